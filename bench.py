@@ -14,9 +14,12 @@ timed region.
 N > 1: layer/channel-range units are LPT-sharded over the ranks (dct_pruning_amd/sharding.py);
 total work is fixed, so scaling = "strong".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the
-dominant kernel (the 56x56 codelet kernel, measured with HIP events on the launch stream
-inside the timed region) and `cpu_baseline` (the oracle's per-map loop on a bounded sample).
+Prints ONE JSON line on rank 0: `value` (Mmaps/s over the K timed steps) and `ms_per_step`. A plain
+run does nothing else: set-up, `--warmup` steps, the `--steps` timed steps, `--dump-outputs` if given,
+the line. `--full` adds `roofline` for the dominant kernel (the 56x56 codelet kernel, measured with
+HIP events on the launch stream inside the timed region), the Parseval and dead-channel checks of
+the result, `all_gather_ms` (N > 1), the `headline` micro-benchmarks and `cpu_baseline` (the
+oracle's per-map loop on a bounded sample).
 """
 import argparse
 import json
@@ -30,7 +33,7 @@ if ROOT not in sys.path:
 
 import torch  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak
 CFG_ID = 4
 
 
@@ -45,8 +48,17 @@ def parse():
     ap.add_argument("--net", default="resnet_50")
     ap.add_argument("--input-size", type=int, default=None,
                     help="u2netp only: input crop edge (reference crop 288, BASELINE config 5 names 320)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-headline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: `roofline` (HIP events around "
+                         "the dominant kernel inside the timed region), the Parseval and dead-channel checks of the result, "
+                         "`all_gather_ms`, the `headline` micro-benchmarks and `cpu_baseline`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-headline", action="store_true", help="with --full: leave out the headline micro-benchmarks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed as DIR/<name>.npy (float32): "
+                         "`scores` (the per-channel running means of every hook point, concatenated in hook order) and "
+                         "`energy` (the last step's per-map energies [batch, channels] of rank 0's tensors); at most "
+                         "64 MiB in all, beyond that a fixed seeded sample of the flattened array")
     ap.add_argument("--per-tensor", action="store_true",
                     help="one energy launch per hooked tensor (default: one dcts_energy_multi_f32 launch per tile shape)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -255,6 +267,28 @@ def headline(lib, dev, stream_ptr, ws_fn):
     return out
 
 
+OUTPUT_BUDGET = 64 << 20  # bytes, all files of --dump-outputs together
+
+
+def write_outputs(d, arrays, budget=OUTPUT_BUDGET):
+    """--dump-outputs: each tensor of `arrays` (name -> tensor) as d/<name>.npy in float32. An array that does not fit
+    its share of `budget` (smallest arrays first, each gets an equal share of what is left) is replaced by the
+    elements of its flattened form at a fixed seeded choice of positions, in ascending order of position."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    left = budget - 128 * len(arrays)  # the .npy header of each file
+    names = sorted(arrays, key=lambda k: arrays[k].numel())
+    for i, name in enumerate(names):
+        t = arrays[name].detach().float()
+        k = left // (4 * (len(names) - i))
+        if t.numel() > k:
+            pick = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            t = t.reshape(-1)[pick.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(d, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -335,6 +369,8 @@ def main():
         bound.append((i, BoundUnit(lib, x, scored[u.layer][2], stream_ptr, ws_fn(N, u.c_hi - u.c_lo, p.H, p.W))))
     if args.steps is None:
         args.steps = 20 if total_cost >= 1e9 else 200
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py needs --steps >= 1 and --warmup >= 0")
     maps_per_step = N * sum(chans)
     per_edge = {}
     for p, ch in zip(points, chans):
@@ -397,8 +433,8 @@ def main():
         mixed = (marr, len(bound))
         dom = [b for _, b in bound]  # one kernel covers every tensor: it is the dominant one
 
-    # timing events are created before the clock starts (creating one costs more host time than recording it)
-    ev_pool = [torch.cuda.Event(enable_timing=True) for _ in range(2 * args.steps * (len(bound) + 2))]
+    # timing events (--full only) are created before the clock starts (creating one costs more host time than recording it)
+    ev_pool = [torch.cuda.Event(enable_timing=True) for _ in range(2 * args.steps * (len(bound) + 2))] if args.full else []
 
     def new_event():
         return ev_pool.pop()
@@ -481,11 +517,11 @@ def main():
     events = []
     barrier()
     t0 = time.perf_counter()
-    # the dominant kernel is timed with HIP events inside the timed region; when a step is tens of
+    # --full: the dominant kernel is timed with HIP events inside the timed region; when a step is tens of
     # microseconds the event packets themselves open gaps between the launches, so only every 8th step is timed
     ev_stride = 1 if total_cost >= 1e9 else 8
     for i_ in range(args.steps):
-        step(events if i_ % ev_stride == 0 else None)
+        step(events if args.full and i_ % ev_stride == 0 else None)
     t_enqueued = time.perf_counter() - t0  # host time to enqueue the K steps (a run is host-bound if this is ~ dt)
     gathered = gather()
     barrier()
@@ -495,38 +531,45 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
 
-    # sanity on the result the timed region produced: Parseval against the inputs (device-side),
-    # and the dead channels of the synthetic tensors (c % 8 == 5) must come out as exactly +0.0
-    i0, b0 = bound[0]
-    ref = (b0.x.double() ** 2).sum(dim=(-2, -1)).mean(0)
-    got = gathered[rank, off[i0]:off[i0] + b0.fr.numel()].double()
-    rel = ((got - ref).abs() / ref.clamp_min(1e-30))[ref > 0].max().item()
-    if not rel <= 1e-4:
-        sys.exit("bench sanity check failed: rel err %g" % rel)
-    dead_bad = 0
-    for i, b in bound:
-        fr = gathered[rank, off[i]:off[i] + b.fr.numel()]
-        dead = (b.x[0].reshape(b.x.shape[1], -1).abs().amax(dim=1) == 0) & (b.x.abs().amax(dim=(0, 2, 3)) == 0)
-        dead_bad += int(((fr[dead] != 0) | torch.signbit(fr[dead])).sum().item())
-    if dead_bad:
-        sys.exit("bench sanity check failed: %d dead channels are not exactly +0.0" % dead_bad)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the score vector of every hook point (all ranks' shares,
+        # gathered) and the per-map energies of the last step (this rank's tensors, in unit order)
+        scores = torch.cat(sharding.unpack(gathered, units, owner, off, chans))
+        energy = torch.cat([b.energy for _, b in sorted(bound, key=lambda ib: ib[0])], dim=1)
+        write_outputs(args.dump_outputs, {"scores": scores, "energy": energy})
 
-    # the collective on its own (reported separately), outside the timed region
-    gather_ms = None
-    if world > 1:
-        barrier()
-        tg = time.perf_counter()
-        gather()
-        barrier()
-        gather_ms = (time.perf_counter() - tg) * 1e3
+    full = {}
+    if args.full:
+        # sanity on the result the timed region produced: Parseval against the inputs (device-side),
+        # and the dead channels of the synthetic tensors (c % 8 == 5) must come out as exactly +0.0
+        i0, b0 = bound[0]
+        ref = (b0.x.double() ** 2).sum(dim=(-2, -1)).mean(0)
+        got = gathered[rank, off[i0]:off[i0] + b0.fr.numel()].double()
+        rel = ((got - ref).abs() / ref.clamp_min(1e-30))[ref > 0].max().item()
+        if not rel <= 1e-4:
+            sys.exit("bench sanity check failed: rel err %g" % rel)
+        dead_bad = 0
+        for i, b in bound:
+            fr = gathered[rank, off[i]:off[i] + b.fr.numel()]
+            dead = (b.x[0].reshape(b.x.shape[1], -1).abs().amax(dim=1) == 0) & (b.x.abs().amax(dim=(0, 2, 3)) == 0)
+            dead_bad += int(((fr[dead] != 0) | torch.signbit(fr[dead])).sum().item())
+        if dead_bad:
+            sys.exit("bench sanity check failed: %d dead channels are not exactly +0.0" % dead_bad)
 
-    # events come in (start, stop) pairs around each contiguous group of dominant-kernel launches
-    dom_ms = sum(events[i].elapsed_time(events[i + 1]) for i in range(0, len(events), 2))
-    timed_steps = len(range(0, args.steps, ev_stride))
-    dom_bytes = sum(b.bytes for b in dom) * timed_steps
-    n_launch = max((len(dom) if args.per_tensor else -(-len(dom) // (48 if mixed is not None else 32))) * timed_steps, 1)
+        # the collective on its own (reported separately), outside the timed region
+        if world > 1:
+            barrier()
+            tg = time.perf_counter()
+            gather()
+            barrier()
+            full["all_gather_ms"] = (time.perf_counter() - tg) * 1e3  # flat buffer fill + one all_gather_into_tensor + barriers
 
-    if rank == 0:
+        # events come in (start, stop) pairs around each contiguous group of dominant-kernel launches
+        dom_ms = sum(events[i].elapsed_time(events[i + 1]) for i in range(0, len(events), 2))
+        timed_steps = len(range(0, args.steps, ev_stride))
+        dom_bytes = sum(b.bytes for b in dom) * timed_steps
+        n_launch = max((len(dom) if args.per_tensor else -(-len(dom) // (48 if mixed is not None else 32))) * timed_steps, 1)
+
         achieved = dom_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
         # HBM bytes per launch of the dominant kernel from the committed PMC passes of THIS bench at THIS launch
         # size (tools/profile_bench_pmc.sh: FETCH_SIZE and WRITE_SIZE in separate rocprofv3 runs, the read side
@@ -536,7 +579,7 @@ def main():
         traffic_note = "no PMC record (profiles/pmc_traffic_bench.json)"
         tpath = os.path.join(ROOT, "profiles", "pmc_traffic_bench.json")
         alg_per_launch = dom_bytes / n_launch
-        if os.path.isfile(tpath):
+        if rank == 0 and os.path.isfile(tpath):
             try:
                 # the record is only valid for the binary it was measured on: it carries the SHA-256 of libdctscore.so
                 # (the build is reproducible: the same sources give the same bytes on any box of this image)
@@ -557,6 +600,15 @@ def main():
             except Exception as exc:
                 traffic = None
                 traffic_note = str(exc)
+        full["roofline"] = {"bound": "hbm",
+                            "kernel": "k_energy_codelet_mixed (edges 2..32)" if mixed is not None else kernel_name(dom_edge, args.per_tensor),
+                            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
+                            "launches": n_launch, "timed_steps": timed_steps, "avg_launch_us": dom_ms / n_launch * 1e3,
+                            "alg_bytes_per_launch": dom_bytes / n_launch}
+        full["parity_check_rel_err"], full["dead_channels_not_plus_zero"] = rel, dead_bad
+
+    if rank == 0:
         res = {
             "metric": "feature-map DCT+score throughput", "value": maps_per_step * args.steps / dt / 1e6,
             "unit": "Mmaps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -570,19 +622,11 @@ def main():
                        "units_rank0": len(bound), "load_imbalance": (max(load) / (sum(load) / world)) if world > 1 else 1.0},
             "GB_s_whole_step": total_cost * args.steps / dt / 1e9,
             "host_enqueue_ms_per_step": t_enqueued / args.steps * 1e3,
-            "roofline": {"bound": "hbm",
-                         "kernel": "k_energy_codelet_mixed (edges 2..32)" if mixed is not None else kernel_name(dom_edge, args.per_tensor),
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
-                         "launches": n_launch, "timed_steps": timed_steps, "avg_launch_us": dom_ms / n_launch * 1e3,
-                         "alg_bytes_per_launch": dom_bytes / n_launch},
-            "parity_check_rel_err": rel, "dead_channels_not_plus_zero": dead_bad,
         }
-        if gather_ms is not None:
-            res["all_gather_ms"] = gather_ms  # flat buffer fill + one all_gather_into_tensor + barriers
-        if not args.no_headline and world == 1:
+        res.update(full)
+        if args.full and not args.no_headline and world == 1:
             res["headline"] = headline(lib, dev, stream_ptr, ws_fn)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(points, args.cpu_seconds)
         print(json.dumps(res))
     if dist is not None:

@@ -26,7 +26,7 @@ def run_bench(*argv, rehearse=False):
 
 
 def test_bench_self_launches_two_ranks():
-    common = ["--batch", "16", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-headline"]
+    common = ["--batch", "16", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-headline"]
     one = run_bench("--gpus", "1", *common)
     two = run_bench("--gpus", "2", *common, rehearse=True)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
@@ -43,7 +43,7 @@ def test_bench_self_launches_two_ranks():
 def test_bench_u2netp_at_320():
     """BASELINE.json config 5 names a 320x320 input (the reference crops to 288)."""
     r = run_bench("--net", "u2netp", "--input-size", "320", "--batch", "2", "--steps", "3", "--warmup", "1",
-                  "--no-cpu-baseline", "--no-headline")
+                  "--full", "--no-cpu-baseline", "--no-headline")
     assert "320x320" in r["config"]["workload"] and r["roofline"]["kernel"].startswith("k_split_fused2")
 
 
@@ -54,7 +54,26 @@ def test_bench_rehearsal_with_four_ranks_and_channel_range_units():
     ranges (bench.py cuts wide layers exactly then) and the sharded result must still pass the device-side
     Parseval check on every rank's share."""
     r = run_bench("--gpus", "4", "--net", "vgg_16_bn", "--batch", "32", "--steps", "5", "--warmup", "2",
-                  "--no-cpu-baseline", "--no-headline", rehearse=True)
+                  "--full", "--no-cpu-baseline", "--no-headline", rehearse=True)
     assert r["n_gpus"] == 4 and r["scaling"] == "strong" and "all_gather_ms" in r
     assert r["parity_check_rel_err"] <= 1e-4 and r["dead_channels_not_plus_zero"] == 0
     assert r["config"]["load_imbalance"] <= 1.10
+
+
+def test_plain_run_times_only_the_steps_and_dumps_its_outputs(tmp_path):
+    """A plain run: `--steps` timed steps, a line without the --full figures, and `--dump-outputs` writes the scores and
+    the last step's energies, identical from run to run; every step sees the same batch, so each score is the mean of
+    its channel's energies."""
+    import numpy as np
+    argv = ["--gpus", "1", "--batch", "16", "--steps", "4", "--warmup", "1"]
+    r = run_bench(*argv, "--dump-outputs", str(tmp_path / "a"))
+    run_bench(*argv, "--dump-outputs", str(tmp_path / "b"))
+    assert r["steps"] == 4 and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["unit"] == "Mmaps/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert not {"roofline", "headline", "cpu_baseline", "parity_check_rel_err"} & set(r)
+    out = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("scores", "energy")}
+    assert out["scores"].shape == (22720,) and out["energy"].shape == (16, 22720)
+    for n, v in out.items():
+        assert v.dtype == np.float32
+        np.testing.assert_array_equal(v, np.load(tmp_path / "b" / (n + ".npy")))
+    np.testing.assert_allclose(out["energy"].mean(0, dtype=np.float64), out["scores"], rtol=1e-5)

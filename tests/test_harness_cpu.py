@@ -87,10 +87,9 @@ def test_single_sweep_equals_per_hook(name, tmp_path, oracle_energy):
 
 
 def test_shipped_reference_files_have_the_same_format():
-    """The 41 .npy files the reference ships (format only; values are not reproducible)."""
-    ref_dir = "/root/reference/importance_score"
-    if not os.path.isdir(ref_dir):
-        pytest.skip("reference tree not present on this box")
+    """The 41 .npy files the reference ships (format only; values are not reproducible), kept as
+    fixtures under tests/golden/reference_importance_score/."""
+    ref_dir = os.path.join(GOLD, "reference_importance_score")
     n = 0
     for sub in os.listdir(ref_dir):
         for f in os.listdir(os.path.join(ref_dir, sub)):

@@ -44,10 +44,9 @@ def test_masks_for_dir_and_compare(tmp_path):
 
 
 def test_on_the_reference_shipped_scores():
-    d = "/root/reference/importance_score/googlenet_limit5"
-    if not os.path.isdir(d):
-        pytest.skip("reference tree not present on this box")
-    m = masks.masks_for_dir(d, 0.4)
+    d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_importance_score",
+                     "googlenet_limit5")
+    m =masks.masks_for_dir(d, 0.4)
     assert len(m) == 37
     for k, v in m.items():
         imp = np.load(os.path.join(d, k + ".npy"))

@@ -12,7 +12,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
   out=gpurun_out/pmcb_${tag}_$c
   rm -rf "$out"; mkdir -p "$out"
   rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$out" -o pmc -- \
-    python3 bench.py --no-headline --no-cpu-baseline --steps 5 --warmup 2 --pmc-calib "$@" > "$out/bench.json" 2> "$out/stderr.txt"
+    python3 bench.py --full --no-headline --no-cpu-baseline --steps 5 --warmup 2 --pmc-calib "$@" > "$out/bench.json" 2> "$out/stderr.txt"
 done
 python3 tools/pmc_bench_traffic.py gpurun_out/pmcb_${tag}_FETCH_SIZE gpurun_out/pmcb_${tag}_WRITE_SIZE > gpurun_out/pmc_traffic_bench_$tag.json
 cat gpurun_out/pmc_traffic_bench_$tag.json
