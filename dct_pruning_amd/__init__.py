@@ -4,7 +4,8 @@ Scope: forward-hooked feature maps [N,C,H,W] -> per-map orthonor
 DCT-II -> sum of squared coefficients -> per-channel running mean -> .npy score files
 (reference: utils/common.py:230-309 and :367-977). The arithmetic runs in hand-written
 gfx950 HIP kernels behind the C ABI of include/dctscore.h; this package is the host-side
-mirror of the reference's hook / imp_score interface.
+mirror of the reference's hook / imp_score interface. A second criterion, the HRank feature-map
+rank (rank_nc, imp_score(criterion="rank")), shares everything above the kernel.
 """
 from .ops import (  # noqa: F401
     ALGO_AUTO,
@@ -23,7 +24,8 @@ from .ops import (  # noqa: F401
     energy_multi,
     energy_nc,
     has_codelet,
+    rank_nc,
     weighted_energy_nc,
 )
 
-__all__ = ["energy_nc", "energy_multi", "energy_mixed", "dct2d", "batch_sum", "has_codelet", "weighted_energy_nc", "ALGO_AUTO", "ALGO_DIRECT", "ALGO_CODELET", "ALGO_SPLIT", "ALGO_PREFETCH", "ALGO_FUSED", "ALGO_PIPE", "ALGO_LANE", "ALGO_TILE2D", "ALGO_RECT"]
+__all__ = ["energy_nc", "energy_multi", "energy_mixed", "dct2d", "batch_sum", "has_codelet", "weighted_energy_nc", "rank_nc", "ALGO_AUTO", "ALGO_DIRECT", "ALGO_CODELET", "ALGO_SPLIT", "ALGO_PREFETCH", "ALGO_FUSED", "ALGO_PIPE", "ALGO_LANE", "ALGO_TILE2D", "ALGO_RECT"]

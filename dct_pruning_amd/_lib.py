@@ -9,7 +9,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdctscore.so")
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _lock = threading.Lock()
 _lib = None
@@ -40,6 +40,7 @@ SIGNATURES = {
     "dcts_energy_multi_f32": (ctypes.c_int, [_vp, _i32, _i64, _i64, _i32, _vp, _sz, _vp]),
     "dcts_energy_mixed_f32": (ctypes.c_int, [_vp, _i32, _vp, _sz, _vp]),
     "dcts_running_mean_update_multi_f32": (ctypes.c_int, [_vp, _i32, _vp]),
+    "dcts_rank_f32": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp]),
     "dcts_debug_stream_read_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
 }
 

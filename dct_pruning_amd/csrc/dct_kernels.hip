@@ -3004,7 +3004,7 @@ const char* dcts_strerror(int code) {
     case DCTS_E_CHANNELS: return "channel slice outside [0, C_total)";
     case DCTS_E_STRIDE: return "rows must be dense: strideW == 1 and strideH >= W";
     case DCTS_E_WORKSPACE: return "workspace missing or smaller than dcts_workspace_bytes()";
-    case DCTS_E_UNSUPPORTED: return "no kernel of the requested family for this shape";
+    case DCTS_E_UNSUPPORTED: return "no kernel of the requested family for this shape (rank: edges up to 64)";
     case DCTS_E_ALIGN: return "pointer not 4-byte aligned (tensors) / 16-byte aligned (workspace)";
     default: break;
   }

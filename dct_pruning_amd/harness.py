@@ -21,7 +21,11 @@ Additions (opt-in, results identical on fixed batches):
                       all tensors of one tile shape are scored in ONE launch
                       (dcts_energy_multi_f32) and all running means in one more;
   world_size > 1      hook points LPT-sharded over ranks, one all-gather at the end,
-                      rank 0 writes the files.
+                      rank 0 writes the files (SURVEY.md §8e);
+  criterion="rank"    HRank's score instead of the DCT energy: the numerical rank of every map
+                      (dcts_rank_f32, ops.rank_nc) through the same hooks, accumulators, schedules and
+                      sharding; files go to rank_conv/<net>_limit<L>/rank_*.npy (hooks
+                      get_feature_hook_rank / get_feature_hook_densenet_rank).
 """
 import os
 
@@ -31,8 +35,11 @@ import torch
 from . import ops, schedules, sharding
 from .accumulate import DeviceAccumulator, DeviceBatchAccumulator, HostAccumulator
 
-# tests swap this for the oracle to exercise the host logic without a GPU
+# tests swap these for the oracle to exercise the host logic without a GPU
 _energy_nc = ops.energy_nc
+_rank_nc = ops.rank_nc
+
+CRITERIA = ("dct", "rank")
 
 # the reference's module globals (utils/common.py:258-259)
 _acc = HostAccumulator()
@@ -49,6 +56,21 @@ def _hook_energy(kind, x):
     if kind == "input":
         return _energy_nc(x, pad_front_if_odd=True)
     return _energy_nc(x)
+
+
+def _hook_rank(kind, x):
+    """HRank's per-map matrix_rank over the same channels as the DCT hook of that kind (no odd pad: the rank is
+    taken of the map as it is)."""
+    if kind == "last12":
+        b = x.shape[1]
+        return _rank_nc(x, c_begin=b - 12, c_count=12)
+    if kind == "input":
+        raise ValueError("the rank criterion has no input hook (U2-Net-p is out of its scope)")
+    return _rank_nc(x)
+
+
+def _hook_score(criterion, kind, x):
+    return _hook_rank(kind, x) if criterion == "rank" else _hook_energy(kind, x)
 
 
 def get_feature_hook(self, input, output):
@@ -82,7 +104,19 @@ def make_weighted_feature_hook(weights_for):
     return hook
 
 
+def get_feature_hook_rank(self, input, output):
+    """HRank's hook: c = [matrix_rank(output[i, j]) for every map]; c.view(a, -1).float().sum(0), then the running
+    mean of utils/common.py:271-277. The ranks are exact small integers in fp32, so the batch sum is exact."""
+    _acc.update(_hook_rank("full", output))
+
+
+def get_feature_hook_densenet_rank(self, input, output):
+    """HRank's densenet hook: channels [b-12, b)."""
+    _acc.update(_hook_rank("last12", output))
+
+
 _HOOKS = {"full": get_feature_hook, "last12": get_feature_hook_densenet, "input": get_feature_hook_u2net_input}
+_RANK_HOOKS = {"full": get_feature_hook_rank, "last12": get_feature_hook_densenet_rank}
 
 
 def _net_device(net):
@@ -146,10 +180,17 @@ def _done_line(net_name, idx, stem):
     return "/" + stem + ":done!"
 
 
-def _save(out_dir, net_name, pt, scores):
+def _file_stem(criterion, stem):
+    """rank files: the schedule's stem with the leading imp_ replaced by rank_ (imp_conv3 -> rank_conv3)."""
+    if criterion == "rank" and stem.startswith("imp_"):
+        return "rank_" + stem[len("imp_"):]
+    return stem
+
+
+def _save(out_dir, net_name, pt, scores, criterion="dct"):
     for stem, lo, hi in pt.files:
         arr = scores if lo is None else scores[lo:hi]
-        np.save(os.path.join(out_dir, stem + ".npy"), arr)
+        np.save(os.path.join(out_dir, _file_stem(criterion, stem) + ".npy"), arr)
         line = _done_line(net_name, 0, stem)
         if line:
             print(line)
@@ -164,8 +205,10 @@ class _PointHook:
     None = the whole hook point under `key`. Per-channel scores do not depend on which call computes them,
     so the pieces concatenate to the unsplit result bit for bit."""
 
-    def __init__(self, kind, accumulate, device, batch=None, key=None, deferred=False, ranges=None, nominal_c=None):
+    def __init__(self, kind, accumulate, device, batch=None, key=None, deferred=False, ranges=None, nominal_c=None,
+                 criterion="dct"):
         self.kind, self.accumulate, self.device, self.acc = kind, accumulate, device, None
+        self.criterion = criterion
         self.batch, self.key, self.deferred = batch, key, deferred
         self.ranges, self.nominal_c, self.accs = ranges, nominal_c, {}
 
@@ -193,7 +236,12 @@ class _PointHook:
             if self.deferred and self.batch is not None:
                 self.batch.add_tensor(key, x, cb, cc, pad)
                 continue
-            e = _hook_energy(self.kind, x) if cb is None else _energy_nc(x, c_begin=cb, c_count=cc, pad_front_if_odd=pad)
+            if cb is None:
+                e = _hook_score(self.criterion, self.kind, x)
+            elif self.criterion == "rank":
+                e = _rank_nc(x, c_begin=cb, c_count=cc)
+            else:
+                e = _energy_nc(x, c_begin=cb, c_count=cc, pad_front_if_odd=pad)
             if self.batch is not None:
                 self.batch.add(key, e)
                 continue
@@ -210,22 +258,31 @@ class _PointHook:
         return np.ascontiguousarray(self.accs[key].scores(), dtype=np.float32)
 
 
-def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host", group=None, deferred=False):
+def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host", group=None, deferred=False,
+              criterion="dct"):
     """Counterpart of utils/common.py:367-977. `args` needs .net, .limit (and whatever
-    load_data reads when train_loader is None)."""
+    load_data reads when train_loader is None). criterion="rank" scores HRank's feature-map rank instead of the
+    DCT energy and writes rank_conv/<net>_limit<L>/rank_*.npy."""
     global _acc
+    if criterion not in CRITERIA:
+        raise ValueError("imp_score: unknown criterion %r (expected one of %s)" % (criterion, ", ".join(CRITERIA)))
+    if criterion == "rank" and deferred:
+        raise ValueError("imp_score: criterion='rank' has no deferred mode; use single_sweep / accumulate instead")
+    if criterion == "rank" and args.net == "u2netp":
+        raise ValueError("imp_score: criterion='rank' supports edges up to 64; u2netp (up to 288) is out of scope")
     if not hasattr(args, "limit"):
         # utils/load_models.py:819 calls imp_score from prune_*.py whose parsers define no --limit
         # (AttributeError in the reference as shipped); fall back to importance_generation.py's default
         args.limit = 5
-    out_dir = "importance_score/" + args.net + "_limit" + str(args.limit)
+    root = "rank_conv" if criterion == "rank" else "importance_score"
+    out_dir = root + "/" + args.net + "_limit" + str(args.limit)
     world, rank = 1, 0
     if group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
         world = torch.distributed.get_world_size(group)
         rank = torch.distributed.get_rank(group)
     if rank == 0:
-        if not os.path.isdir("importance_score"):
-            os.mkdir("importance_score")
+        if not os.path.isdir(root):
+            os.mkdir(root)
         if not os.path.isdir(out_dir):
             os.mkdir(out_dir)
 
@@ -252,7 +309,8 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
     # cutting it would repeat its forward sweep on another rank.
     scored = [schedules.scored_shape(p) for p in pts]
     chans = [sc[1] for sc in scored]
-    cost_pc = [float(p.H * p.W) for p in pts]
+    # LPT cost per channel: the bytes the DCT kernels stream, or the rank kernel's O(H W min(H, W)) arithmetic
+    cost_pc = [float(p.H * p.W * min(p.H, p.W)) if criterion == "rank" else float(p.H * p.W) for p in pts]
     if world > 1:
         total_cost = sum(c * k for c, k in zip(chans, cost_pc))
         cut = total_cost / (8.0 * world) if single_sweep else None  # G = 8: every net within 6 % of balance
@@ -279,7 +337,7 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
             whole = per_layer[i] == 1
             hooks[i] = _PointHook(pts[i].kind, accumulate, dev, batch=batch, key=ks[0], deferred=deferred,
                                   ranges=None if whole else [(k, units[k].c_lo, units[k].c_hi) for k in ks],
-                                  nominal_c=chans[i])
+                                  nominal_c=chans[i], criterion=criterion)
             handles.append(_resolve(net, pts[i].module).register_forward_hook(hooks[i]))
         sweep(net, train_loader, args.limit)
         for h in handles:
@@ -295,19 +353,19 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
                 print("current layer:", "net." + pt.module)
             layer = _resolve(net, pt.module)
             if accumulate == "device":
-                hook = _PointHook(pt.kind, accumulate, dev, key=k)
+                hook = _PointHook(pt.kind, accumulate, dev, key=k, criterion=criterion)
                 handler = layer.register_forward_hook(hook)
                 sweep(net, train_loader, args.limit)
                 handler.remove()
                 results[k] = hook.scores()
             else:
-                handler = layer.register_forward_hook(_HOOKS[pt.kind])
+                handler = layer.register_forward_hook((_RANK_HOOKS if criterion == "rank" else _HOOKS)[pt.kind])
                 sweep(net, train_loader, args.limit)
                 handler.remove()
                 results[k] = np.ascontiguousarray(_acc.feature_result.numpy(), dtype=np.float32)
                 _acc.reset()
             if world == 1:
-                _save(out_dir, args.net, pt, results[k])
+                _save(out_dir, args.net, pt, results[k], criterion)
         if world == 1:
             print("The importance score generation has been completed!")  # utils/common.py:977
             return
@@ -320,7 +378,7 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
         for i, pt in enumerate(pts):
             if args.net == "u2netp":
                 print("current layer:", "net." + pt.module)
-            _save(out_dir, args.net, pt, layer_scores[i])
+            _save(out_dir, args.net, pt, layer_scores[i], criterion)
         print("The importance score generation has been completed!")
     if world > 1:
         torch.distributed.barrier(group)

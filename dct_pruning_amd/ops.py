@@ -198,3 +198,27 @@ def weighted_energy_nc(x, weights, c_begin=0, c_count=None, pad_front_if_odd=Fal
             x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3), c_begin, c_count,
             1 if pad_front_if_odd else 0, weights.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), stream))
     return out
+
+
+def rank_nc(x, c_begin=0, c_count=None, out=None):
+    """R[n, j] = numerical rank of x[n, c_begin+j] -> [N, c_count] fp32 (exact integers; all-zero map: +0.0).
+
+    The HRank criterion (dcts_rank_f32): #{sigma_i > max(H, W) * 2^-23 * sigma_max}, the default rule of
+    torch.linalg.matrix_rank for fp32, computed in fp64. Edges up to 64 on each axis.
+    Enqueues on the current stream of x's device; no synchronisation.
+    """
+    _check_input(x)
+    c_begin, c_count = _slice(x, c_begin, c_count)
+    N, C, H, W = x.shape
+    if out is None:
+        out = torch.empty((N, c_count), dtype=torch.float32, device=x.device)
+    elif out.shape != (N, c_count) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous float32 [N, c_count] tensor on x's device")
+    if x.stride(3) != 1 or x.stride(2) < W:
+        x = x.contiguous()
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    with torch.cuda.device(x.device):
+        code = _lib.load().dcts_rank_f32(x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+                                         c_begin, c_count, out.data_ptr(), stream)
+    _lib.check(code)
+    return out

@@ -7,7 +7,9 @@ prune_imagenet.py / prune_u2netp.py read through --imp_score. The DCT+score arit
 in libdctscore (HIP, gfx950); a GPU is required.
 
 Extra, opt-in flags: --synthetic (seeded synthetic batches; also lifts the need for a
-checkpoint), --input_size, --seed, --single_sweep, --device_accumulate, --deferred. Multi-GPU: launch with
+checkpoint), --input_size, --seed, --single_sweep, --device_accumulate, --deferred, --criterion {dct,rank}
+(rank: HRank's feature-map rank instead of the DCT energy, written to rank_conv/<net>_limit<L>/rank_*.npy;
+edges up to 64, so not with --net u2netp, and not with --deferred). Multi-GPU: launch with
 `python -m torch.distributed.run --nproc-per-node G importance_generation.py ...` — hook points
 are sharded over the ranks and rank 0 writes the files.
 """
@@ -39,7 +41,14 @@ def parse_args(argv=None):
     parser.add_argument("--device_accumulate", action="store_true", help="keep the running mean on the GPU")
     parser.add_argument("--deferred", action="store_true",
                         help="single sweep, one scoring launch per tile shape per batch (implies the two above)")
-    return parser.parse_args(argv)
+    parser.add_argument("--criterion", type=str, default="dct", choices=("dct", "rank"),
+                        help="dct: DCT energy (importance_score/); rank: HRank feature-map rank (rank_conv/)")
+    args = parser.parse_args(argv)
+    if args.criterion == "rank" and args.net == "u2netp":
+        parser.error("--criterion rank supports feature maps up to 64 x 64; --net u2netp is out of its scope")
+    if args.criterion == "rank" and args.deferred:
+        parser.error("--criterion rank has no --deferred mode (use --single_sweep / --device_accumulate)")
+    return args
 
 
 def load_checkpoint(net, args):
@@ -90,7 +99,8 @@ def main(argv=None):
     net = net.to(dev)
 
     harness.imp_score(net, args, single_sweep=args.single_sweep,
-                      accumulate="device" if args.device_accumulate else "host", deferred=args.deferred)
+                      accumulate="device" if args.device_accumulate else "host", deferred=args.deferred,
+                      criterion=args.criterion)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -42,8 +42,9 @@ extern "C" {
 #endif
 
 /* 2: workspace contract (the library may leave basis tables in a workspace between calls; 16-byte
- *    alignment; dcts_workspace_invalidate[_range]), multi / mixed / weighted entry points. */
-#define DCTS_ABI_VERSION 2
+ *    alignment; dcts_workspace_invalidate[_range]), multi / mixed / weighted entry points.
+ * 3: dcts_rank_f32 (the HRank criterion) and DCTS_RANK_MAX_EDGE. */
+#define DCTS_ABI_VERSION 3
 
 enum {
   DCTS_OK = 0,
@@ -246,6 +247,20 @@ typedef struct dcts_update_desc {
   int32_t reserved;
 } dcts_update_desc;
 int dcts_running_mean_update_multi_f32(const dcts_update_desc* descs, int32_t count, void* stream);
+
+/*
+ * Second scoring criterion (HRank; the reference keeps it as a commented alternative, utils/common.py:268):
+ *   out_nc[n*c_count + j] = numerical rank of x[n, c_begin+j], as an exact fp32 integer (all-zero map: +0.0):
+ *   the number of singular values sigma_i > max(H, W) * 2^-23 * sigma_max of the fp32 H x W map - the default
+ *   rule of torch.linalg.matrix_rank for fp32. Computed in fp64 from the Gram matrix of the map (rank.hip).
+ * Addressing as for dcts_energy_f32 (strideW == 1, strideH >= W; no odd pad). Edges 1 ... DCTS_RANK_MAX_EDGE
+ * on each axis; an edge in DCTS_RANK_MAX_EDGE+1 ... DCTS_MAX_EDGE returns DCTS_E_UNSUPPORTED. No workspace,
+ * no host-side state; the result of a map does not depend on N, the channel slice or the other maps.
+ */
+#define DCTS_RANK_MAX_EDGE 64
+int dcts_rank_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                  int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
+                  int32_t c_begin, int32_t c_count, float* out_nc, void* stream);
 
 /*
  * Measurement aid (not on the score path): reads n floats once with the kernels' own access
