@@ -1,0 +1,919 @@
+// api.hip - the C ABI of include/dctscore.h: argument validation, the choice of a kernel family for a shape, the typed
+// dispatch into the family units (dcts_internal.h, rect.h), and the kernels that belong to no family.
+//
+// Replaces the per-map Python loop of the reference hooks (utils/common.py:262-309):
+//   c = [dct.dct_2d(output[i,j,:,:], norm='ortho') ...]; torch.sum(dct.mul(dct)).item()
+// with one launch per hooked tensor: every (sample, channel) map gets its orthonormal
+// 2-D DCT-II and the squared coefficients are reduced to one fp32 energy per map.
+//
+// The kernel families are units of their own (codelet.hip, split.hip, fused.hip, fused2.hip, pipe.hip, tile2d.hip,
+// tile2g.hip, rect.hip, rank.hip). Here:
+//   k_energy_direct   any (H, W) <= DCTS_MAX_EDGE: separable cosine-matrix transform with
+//                     the basis block staged in LDS; intermediate tile in a caller-provided
+//                     workspace (L2-resident). O(H*W*(H+W)) flops per map: the correct
+//                     fallback, compute-bound for large tiles.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <mutex>
+
+#include "../../include/dctscore.h"
+#include "dcts_internal.h"
+#include "rect.h"
+#ifdef DCTS_FUSED_STAMPS
+#include "split_common.hpp"  // g_fused_stamps
+#endif
+
+using namespace dctsi;
+
+namespace {
+
+// ---------------------------------------------------------------------------------------
+// direct family: basis tables + separable transform
+// ---------------------------------------------------------------------------------------
+// Bt[r*n + k] = s_k cos(pi (2r+1) k / (2n)), s_0 = sqrt(1/n), s_k = sqrt(2/n)
+__global__ void k_basis(float* __restrict__ Bt, int n) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * n) return;
+  const int r = idx / n, k = idx - r * n;
+  const long long num = ((long long)(2 * r + 1) * k) % (4LL * n);
+  const double cv = cospi(double(num) / double(2 * n));
+  const double s = (k == 0) ? sqrt(1.0 / double(n)) : sqrt(2.0 / double(n));
+  Bt[idx] = float(cv * s);
+}
+
+constexpr int kDirectThreads = 256;
+constexpr int kKB = 8;  // output rows per basis block
+
+template <bool STORE_COEFF>
+__global__ __launch_bounds__(kDirectThreads) void k_energy_direct(
+    MapGeom g, int pad, const float* __restrict__ CHt, const float* __restrict__ CWt,
+    float* __restrict__ T, float* __restrict__ out) {
+  const int HP = g.H + pad, WP = g.W + pad;
+  __shared__ __attribute__((aligned(16))) float Bs[DCTS_MAX_EDGE][kKB];
+  __shared__ float red[kDirectThreads / 64];
+  const int tid = threadIdx.x;
+  float* Tm = T + (size_t)blockIdx.x * HP * WP;
+
+  for (long long m = blockIdx.x; m < g.nmaps; m += gridDim.x) {
+    const float* xm = map_base(g, m);
+    // ---- phase 1: Tm[k][c] = sum_r CH[k][r] x'[r][c] --------------------------------
+    for (int k0 = 0; k0 < HP; k0 += kKB) {
+      __syncthreads();
+      for (int i = tid; i < HP * kKB; i += kDirectThreads) {
+        const int r = i / kKB, kk = i - r * kKB;
+        Bs[r][kk] = (k0 + kk < HP) ? CHt[r * HP + k0 + kk] : 0.f;
+      }
+      __syncthreads();
+      for (int c = tid; c < WP; c += kDirectThreads) {
+        float acc[kKB];
+#pragma unroll
+        for (int kk = 0; kk < kKB; ++kk) acc[kk] = 0.f;
+        if (c >= pad) {
+          const float* col = xm + (c - pad);
+          for (int r = pad; r < HP; ++r) {
+            const float xv = col[(long long)(r - pad) * g.strideH];
+            const float4 b0 = *reinterpret_cast<const float4*>(&Bs[r][0]);
+            const float4 b1 = *reinterpret_cast<const float4*>(&Bs[r][4]);
+            acc[0] = fmaf(xv, b0.x, acc[0]);
+            acc[1] = fmaf(xv, b0.y, acc[1]);
+            acc[2] = fmaf(xv, b0.z, acc[2]);
+            acc[3] = fmaf(xv, b0.w, acc[3]);
+            acc[4] = fmaf(xv, b1.x, acc[4]);
+            acc[5] = fmaf(xv, b1.y, acc[5]);
+            acc[6] = fmaf(xv, b1.z, acc[6]);
+            acc[7] = fmaf(xv, b1.w, acc[7]);
+          }
+        }
+#pragma unroll
+        for (int kk = 0; kk < kKB; ++kk)
+          if (k0 + kk < HP) Tm[(k0 + kk) * WP + c] = acc[kk];
+      }
+    }
+    // ---- phase 2: Y[k][l] = sum_c Tm[k][c] CW[l][c]; energy += Y^2 --------------------
+    float e = 0.f;
+    for (int k0 = 0; k0 < HP; k0 += kKB) {
+      __syncthreads();  // also orders phase-1 global stores before these loads (same CU)
+      for (int i = tid; i < WP * kKB; i += kDirectThreads) {
+        const int cc = i / kKB, kk = i - cc * kKB;
+        Bs[cc][kk] = (k0 + kk < HP) ? Tm[(k0 + kk) * WP + cc] : 0.f;
+      }
+      __syncthreads();
+      for (int l = tid; l < WP; l += kDirectThreads) {
+        float acc[kKB];
+#pragma unroll
+        for (int kk = 0; kk < kKB; ++kk) acc[kk] = 0.f;
+        for (int cc = 0; cc < WP; ++cc) {
+          const float wv = CWt[cc * WP + l];
+          const float4 b0 = *reinterpret_cast<const float4*>(&Bs[cc][0]);
+          const float4 b1 = *reinterpret_cast<const float4*>(&Bs[cc][4]);
+          acc[0] = fmaf(wv, b0.x, acc[0]);
+          acc[1] = fmaf(wv, b0.y, acc[1]);
+          acc[2] = fmaf(wv, b0.z, acc[2]);
+          acc[3] = fmaf(wv, b0.w, acc[3]);
+          acc[4] = fmaf(wv, b1.x, acc[4]);
+          acc[5] = fmaf(wv, b1.y, acc[5]);
+          acc[6] = fmaf(wv, b1.z, acc[6]);
+          acc[7] = fmaf(wv, b1.w, acc[7]);
+        }
+#pragma unroll
+        for (int kk = 0; kk < kKB; ++kk) {
+          if (k0 + kk < HP) {
+            if constexpr (STORE_COEFF)
+              out[(m * HP + k0 + kk) * WP + l] = acc[kk];
+            else
+              e = fmaf(acc[kk], acc[kk], e);
+          }
+        }
+      }
+    }
+    if constexpr (!STORE_COEFF) {
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) e += __shfl_down(e, off, 64);
+      __syncthreads();
+      if ((tid & 63) == 0) red[tid >> 6] = e;
+      __syncthreads();
+      if (tid == 0) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < kDirectThreads / 64; ++i) s += red[i];
+        out[m] = s;
+      }
+    }
+  }
+}
+
+// Batch sum over n of E[n][j] for a 32-channel strip per block: kSumSl = 16 n-slices run in parallel
+// (slice s takes n = s, s+16, ...), partials are combined in slice order -> a fixed,
+// launch-independent summation order (bit-reproducible, no atomics).
+constexpr int kSumCh = 32, kSumSl = 16;
+__device__ __forceinline__ float strip_batch_sum(const float* __restrict__ e, long long N,
+                                                 long long C, long long j, int slice,
+                                                 float (*part)[kSumCh]) {
+  float s = 0.f;
+  if (j < C) {
+    long long n = slice;
+    // sixteen loads in flight per lane and round trip (a batch of 256 samples is ONE round trip: the
+    // kernel is pure latency, 3.8 us with four loads per trip); the additions keep their order
+#pragma unroll 1
+    for (; n + 15 * kSumSl < N; n += 16 * kSumSl) {
+      float a[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) a[i] = e[(n + i * kSumSl) * C + j];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s += a[i];
+    }
+#pragma unroll 1
+    for (; n + 3 * kSumSl < N; n += 4 * kSumSl) {
+      const float a0 = e[n * C + j], a1 = e[(n + kSumSl) * C + j];
+      const float a2 = e[(n + 2 * kSumSl) * C + j], a3 = e[(n + 3 * kSumSl) * C + j];
+      s += a0;
+      s += a1;
+      s += a2;
+      s += a3;
+    }
+    for (; n < N; n += kSumSl) s += e[n * C + j];
+  }
+  part[slice][threadIdx.x % kSumCh] = s;
+  __syncthreads();
+  float t = 0.f;
+  if (slice == 0) {
+#pragma unroll
+    for (int i = 0; i < kSumSl; ++i) t += part[i][threadIdx.x % kSumCh];
+  }
+  return t;  // valid in slice 0
+}
+
+// out_c[j] = sum_n e[n*C + j]
+__global__ __launch_bounds__(kSumCh * kSumSl) void k_batch_sum(const float* __restrict__ e, long long N,
+                                                               long long C, float* __restrict__ out_c) {
+  __shared__ float part[kSumSl][kSumCh];
+  const int slice = threadIdx.x / kSumCh;
+  const long long j = (long long)blockIdx.x * kSumCh + threadIdx.x % kSumCh;
+  const float t = strip_batch_sum(e, N, C, j, slice, part);
+  if (slice == 0 && j < C) out_c[j] = t;
+}
+
+// fr[j] <- (fr[j] * total + sum_n e[n*C + j]) / (total + N): the running-mean update of
+// utils/common.py:274-277 fused with the batch sum of :273 (same three fp32 roundings)
+__global__ __launch_bounds__(kSumCh * kSumSl) void k_running_mean(const float* __restrict__ e, long long N,
+                                                                  long long C, float* __restrict__ fr,
+                                                                  float total) {
+  __shared__ float part[kSumSl][kSumCh];
+  const int slice = threadIdx.x / kSumCh;
+  const long long j = (long long)blockIdx.x * kSumCh + threadIdx.x % kSumCh;
+  const float t = strip_batch_sum(e, N, C, j, slice, part);
+  if (slice == 0 && j < C) {
+    const float acc = __fadd_rn(__fmul_rn(fr[j], total), t);
+    fr[j] = __fdiv_rn(acc, __fadd_rn(total, float(N)));
+  }
+}
+
+// the same update for up to kMultiMax hook points in one launch (descriptors by value in the
+// kernel arguments): blockIdx.y = hook point, blockIdx.x = 32-channel strip
+constexpr int kMultiMax = 64;
+struct UpdateBatch {
+  dcts_update_desc d[kMultiMax];
+};
+__global__ __launch_bounds__(kSumCh * kSumSl) void k_running_mean_multi(UpdateBatch b) {
+  __shared__ float part[kSumSl][kSumCh];
+  const dcts_update_desc d = b.d[blockIdx.y];
+  if ((long long)blockIdx.x * kSumCh >= d.C_count) return;  // whole block leaves together
+  const int slice = threadIdx.x / kSumCh;
+  const long long j = (long long)blockIdx.x * kSumCh + threadIdx.x % kSumCh;
+  const float t = strip_batch_sum(d.energy_nc, d.N, d.C_count, j, slice, part);
+  if (slice == 0 && j < d.C_count) {
+    const float acc = __fadd_rn(__fmul_rn(d.feature_result[j], d.total_before), t);
+    d.feature_result[j] = __fdiv_rn(acc, __fadd_rn(d.total_before, float(d.N)));
+  }
+}
+
+// Score variant in the coefficient domain: out[m] = sum_{u,v} weights[u,v] * coeff[m][u][v]^2.
+// One wave per map over dense [HW] coefficient tiles; lanes stride the tile, fixed-order wave sum.
+__global__ __launch_bounds__(256) void k_weighted_energy(const float* __restrict__ coeff, const float* __restrict__ weights,
+                                                         long long nmaps, int hw, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+  for (long long m = wave; m < nmaps; m += nwaves) {
+    const float* c = coeff + m * hw;
+    float e = 0.f;
+    for (int i = lane; i < hw; i += 64) {
+      const float v = c[i];
+      e = fmaf(weights[i] * v, v, e);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) e += __shfl_down(e, off, 64);
+    if (lane == 0) out[m] = e;
+  }
+}
+
+// PMC calibration aid: streams n floats with the codelet kernels' access width (one dword per
+// lane, consecutive lanes consecutive addresses) so FETCH_SIZE can be compared with a known
+// byte count in this exact pattern (MI355X_MICROARCH.md, HBM section: widths other than
+// 16 B/lane are uncalibrated).
+__global__ __launch_bounds__(256) void k_calib_read(const float* __restrict__ x, long long n,
+                                                    float* __restrict__ sink) {
+  float s = 0.f;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x)
+    s += x[i];
+  if (s == 123456.789f) sink[0] = s;  // keeps the loads alive without a store in practice
+}
+
+// ---------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------
+constexpr int kDirectGridCap = 512;
+
+struct DirectWs {
+  size_t off_ch, off_cw, off_t, total;
+  int grid;
+};
+DirectWs direct_ws(long long nmaps, int HP, int WP) {
+  DirectWs w;
+  w.grid = (int)(nmaps < kDirectGridCap ? (nmaps > 0 ? nmaps : 1) : kDirectGridCap);
+  w.off_ch = 0;
+  w.off_cw = align_up(w.off_ch + (size_t)HP * HP * 4, 256);
+  w.off_t = align_up(w.off_cw + (size_t)WP * WP * 4, 256);
+  w.total = align_up(w.off_t + (size_t)w.grid * HP * WP * 4, 256);
+  return w;
+}
+
+// dense, 16-byte aligned, even-edge square tiles take the prefetching kernel
+bool dma_ok(int HP, int WP, int pad, const MapGeom& g) {
+  if (pad || HP != WP || (HP % 2) != 0) return false;
+  if (!g.contiguous || g.strideC != (long long)HP * WP) return false;
+  return (reinterpret_cast<uintptr_t>(g.x + (long long)g.c_begin * g.strideC) & 15) == 0;
+}
+
+bool has_tile2d(long long N) { return N == 224 || has_tile2g((int)N) != 0; }
+
+// Does AUTO take the several-maps-per-round 2-D split (tile2g.hip, family 5) for `nmaps` maps of edge HP? Same box,
+// % of the HBM peak, fused / pipelined kernel -> tile2g: 72: 30.9 -> 44.1 (9645 maps), 29.7 -> 45.1 (32768); 80: 33.2 ->
+// 40.3, 32.9 -> 37.6; 144: 30.1 -> 33.7 (2411), 32.0 -> 42.4 (4992), 31.8 -> 41.0 (8192); 160: 31.2 -> 34.1 (1953), 33.5 ->
+// 37.3 (4096); 128: 45.1 -> 43.3 (3051) but 44.1 -> 50.6 (8192); 112: 38.8 -> 34.6, 39.8 -> 38.2
+// (profiles/r03_tile2g_vs_fused_same_box.txt). The choice must not depend on the map count: dcts_energy_multi_f32
+// promises the bits of one call per tensor, whatever the tensors' sizes. So 72, 80, 144, 160 take it, 112 and 128
+// keep the fused / pipelined kernels (DCTS_ALGO_TILE2D still selects it for them).
+bool tile2g_auto(int HP, long long /*nmaps*/) {
+  return has_tile2g(HP) && HP != 96 && HP != 112 && HP != 128;
+}
+
+// which single-launch large-tile kernel serves an edge: 0 none, 1 fused, 2 fused with two roles per
+// wave, 3 pipelined (AUTO order: pipelined, two-roles, fused)
+int tile_family(int HP, int algo, long long nmaps) {
+  if (algo == DCTS_ALGO_TILE2D) return HP == 224 ? 4 : (has_tile2g(HP) ? 5 : 0);
+  if (algo == DCTS_ALGO_AUTO && tile2g_auto(HP, nmaps)) return 5;
+  // AUTO order: 2-D split (tile2d.hip), pipelined, two-roles, fused. 224: 2-D split 33-42 % of the HBM
+  // peak against 31-37 % pipelined, same box, 996...16384 maps
+  if (algo == DCTS_ALGO_AUTO && HP == 224) return 4;
+  if (algo == DCTS_ALGO_PIPE) return has_pipe(HP) && has_fused(HP) ? 3 : 0;
+  if (algo == DCTS_ALGO_AUTO && has_pipe(HP) && has_fused(HP)) return 3;
+  if (has_fused2(HP)) return 2;  // AUTO uses the two-roles-per-wave fused kernel where it exists (288: 31 % vs 18 %, 320: 31 % vs 17 % of the HBM peak)
+  if (has_fused(HP)) return 1;
+  return 0;
+}
+int dispatch_tile_family(int fam, int HP, const TileBatch& tb, hipStream_t st) {
+  switch (fam) {
+    case 6:
+      return dispatch_tile2g_pad(HP, tb, st);
+    case 5:
+      return dispatch_tile2g(HP, tb, st);
+    case 4:
+      return dispatch_tile2d(HP, tb, st);
+    case 3:
+      return dispatch_pipe(HP, tb, st);
+    case 2:
+      return dispatch_fused2(HP, tb, st);
+    case 1:
+      return dispatch_fused(HP, tb, st);
+    default:
+      return DCTS_E_UNSUPPORTED;
+  }
+}
+
+// The direct kernel's basis tables live at the head of the caller's workspace. They are built once per
+// (workspace, stream, H', W') and reused by later calls: the library remembers - on the host, nothing is read
+// back - which BYTE RANGE of which workspace holds tables, and forgets an entry whenever any of its own paths
+// is about to write bytes that overlap that range (another shape's tables, the direct kernel's T tiles, the
+// split path's intermediate, the coefficient path's leaf outputs, the weighted path's coefficient chunk) or the
+// caller says so (dcts_workspace_invalidate[_range]). Same stream only: that is what orders the build before
+// the reuse. Calls that receive an INTERIOR pointer of a caller's workspace (the weighted path's inner calls)
+// never cache: an interior offset depends on the tile shape, and the caller cannot name it to invalidate it.
+struct BasisSlot {
+  uintptr_t lo, hi;  // bytes [lo, hi) hold the two tables
+  void* ws;          // the workspace pointer the call was made with
+  void* stream;
+  int HP, WP;
+};
+constexpr int kBasisSlots = 16;
+BasisSlot g_basis[kBasisSlots] = {};
+int g_basis_next = 0;
+std::mutex g_basis_mu;
+
+bool basis_cached(void* ws, void* stream, int HP, int WP) {
+  std::lock_guard<std::mutex> lk(g_basis_mu);
+  for (const BasisSlot& b : g_basis)
+    if (b.hi && b.ws == ws && b.stream == stream && b.HP == HP && b.WP == WP) return true;
+  return false;
+}
+// forget every entry whose tables overlap [p, p + bytes)
+void basis_forget_range(const void* p, size_t bytes) {
+  if (!p || !bytes) return;
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(p), hi = lo + bytes;
+  std::lock_guard<std::mutex> lk(g_basis_mu);
+  for (BasisSlot& b : g_basis)
+    if (b.hi && b.lo < hi && lo < b.hi) b = BasisSlot{};
+}
+// the caller names a workspace by its base pointer only: forget what was cached under that pointer and
+// whatever tables contain that address
+void basis_forget(void* ws) {
+  if (!ws) return;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(ws);
+  std::lock_guard<std::mutex> lk(g_basis_mu);
+  for (BasisSlot& b : g_basis)
+    if (b.hi && (b.ws == ws || (b.lo <= a && a < b.hi))) b = BasisSlot{};
+}
+void basis_remember(void* ws, const void* tables, size_t table_bytes, void* stream, int HP, int WP) {
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(tables), hi = lo + table_bytes;
+  std::lock_guard<std::mutex> lk(g_basis_mu);
+  for (BasisSlot& b : g_basis)
+    if (b.hi && (b.ws == ws || (b.lo < hi && lo < b.hi))) b = BasisSlot{};  // one shape per workspace, no overlapping tables
+  g_basis[g_basis_next] = BasisSlot{lo, hi, ws, stream, HP, WP};
+  g_basis_next = (g_basis_next + 1) % kBasisSlots;
+}
+
+template <bool STORE>
+int run(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN,
+        int64_t strideC, int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count,
+        int32_t pad_front_if_odd, float* out, void* workspace, size_t workspace_bytes,
+        void* stream, int32_t algo, bool cache_basis = true) {
+  if (!x || !out) return DCTS_E_NULL;
+  if (N <= 0 || C_total <= 0 || H <= 0 || W <= 0) return DCTS_E_SHAPE;
+  if (c_count <= 0 || c_begin < 0 || (int64_t)c_begin + c_count > C_total) return DCTS_E_CHANNELS;
+  if (strideW != 1 || strideH < W) return DCTS_E_STRIDE;
+  if ((reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(out) & 3)) return DCTS_E_ALIGN;
+  const int pad = (pad_front_if_odd && (H % 2 != 0)) ? 1 : 0;
+  const int64_t HP = H + pad, WP = W + pad;
+  if (HP > DCTS_MAX_EDGE || WP > DCTS_MAX_EDGE) return DCTS_E_SHAPE;
+  if (N * (int64_t)c_count >= (1LL << 40)) return DCTS_E_SHAPE;
+
+  MapGeom g;
+  g.x = x;
+  g.nmaps = N * (int64_t)c_count;
+  g.strideN = strideN;
+  g.strideC = strideC;
+  g.strideH = strideH;
+  g.c_count = c_count;
+  g.c_begin = c_begin;
+  g.H = (int)H;
+  g.W = (int)W;
+  g.contiguous = (N == 1 || strideN == (int64_t)c_count * strideC) ? 1 : 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+
+  const bool codelet_ok = has_codelet(HP, WP) && strideH == W;
+  if ((algo == DCTS_ALGO_CODELET || algo == DCTS_ALGO_PREFETCH) && !codelet_ok) return DCTS_E_UNSUPPORTED;
+  if (algo != DCTS_ALGO_AUTO && algo != DCTS_ALGO_DIRECT && algo != DCTS_ALGO_CODELET &&
+      algo != DCTS_ALGO_SPLIT && algo != DCTS_ALGO_PREFETCH && algo != DCTS_ALGO_FUSED && algo != DCTS_ALGO_PIPE && algo != DCTS_ALGO_LANE && algo != DCTS_ALGO_TILE2D && algo != DCTS_ALGO_RECT)
+    return DCTS_E_UNSUPPORTED;
+  if (algo == DCTS_ALGO_LANE && !(codelet_ok && !STORE && pad == 0 && has_lane_kernel((int)HP))) return DCTS_E_UNSUPPORTED;
+  // both edges have a 1-D codelet, but the maps are not square or their rows not dense: the run-time pair of codelets
+  // (rect.hip). Square dense maps keep their own kernels unless ALGO_RECT asks (tests compare the two).
+  const bool rect_ok = HP <= 64 && WP <= 64 && has_rect((int)HP, (int)WP) != 0;
+  if (algo == DCTS_ALGO_RECT && !rect_ok) return DCTS_E_UNSUPPORTED;
+  if (rect_ok && (algo == DCTS_ALGO_RECT || (algo == DCTS_ALGO_AUTO && !codelet_ok))) {
+    RectGeom r{};
+    r.x = x;
+    r.nmaps = g.nmaps;
+    r.strideN = strideN;
+    r.strideC = strideC;
+    r.strideH = strideH;
+    r.c_count = c_count;
+    r.c_begin = c_begin;
+    r.H = (int)H;
+    r.W = (int)W;
+    r.HP = (int)HP;
+    r.WP = (int)WP;
+    r.pad = pad;
+    r.contiguous = g.contiguous;
+    return dispatch_rect(r, out, STORE ? 1 : 0, st);
+  }
+  if (codelet_ok && algo != DCTS_ALGO_DIRECT) {
+    if constexpr (!STORE) {
+      if ((algo == DCTS_ALGO_AUTO || algo == DCTS_ALGO_LANE) && pad == 0 && has_lane_kernel((int)HP)) {
+        MultiGeom mg;
+        for (int i = 0; i < kMultiItems; ++i) {
+          mg.it[i].g = g;
+          mg.it[i].out = out;
+          mg.it[i].group_begin = 0;
+        }
+        mg.total_groups = (g.nmaps + 63) / 64;
+        mg.count = 1;
+        return dispatch_lane((int)HP, mg, st);
+      }
+      // the prefetching variant is opt-in: on MI355X it measured equal to the register-load
+      // kernel in steady state (both at the practical HBM rate) and ~2 % slower on the bench
+      if (algo == DCTS_ALGO_PREFETCH) {
+        if (!dma_ok((int)HP, (int)WP, pad, g)) return DCTS_E_UNSUPPORTED;
+        return dispatch_codelet_dma((int)HP, g, out, st);
+      }
+    } else if (algo == DCTS_ALGO_PREFETCH) {
+      return DCTS_E_UNSUPPORTED;
+    }
+    return dispatch_codelet(STORE ? 1 : 0, (int)HP, (int)WP, pad, g, out, st);
+  }
+  if constexpr (!STORE) {
+    // every split kernel stages with 16-byte direct-to-LDS loads: a base that is only 4-byte aligned takes the
+    // direct kernel - except where tile2g.hip has the shape: it gathers single dwords and needs neither the alignment
+    // nor (for 71 / 79 / 143 / 159: the cv2 path on odd maps) an unpadded tile
+    const bool aligned16 = (reinterpret_cast<uintptr_t>(x + (long long)c_begin * strideC) & 15) == 0;
+    const bool dense_maps = H == W && strideH == W && g.contiguous && strideC == H * W;
+    const bool split_ok = has_split(HP, WP) && pad == 0 && dense_maps && aligned16;
+    if (algo == DCTS_ALGO_SPLIT && !split_ok) return DCTS_E_UNSUPPORTED;
+    if (algo == DCTS_ALGO_AUTO || algo == DCTS_ALGO_FUSED || algo == DCTS_ALGO_PIPE || algo == DCTS_ALGO_TILE2D) {
+      int fam = (split_ok && aligned16) ? tile_family((int)HP, algo, g.nmaps) : 0;
+      if (!fam && dense_maps && (algo == DCTS_ALGO_AUTO || algo == DCTS_ALGO_TILE2D || algo == DCTS_ALGO_FUSED)) {
+        const bool t2 = algo != DCTS_ALGO_FUSED, fu = algo != DCTS_ALGO_TILE2D;  // an explicit family request is kept
+        if (t2 && pad == 0 && !aligned16 && has_tile2g((int)HP)) fam = 5;
+        if (!fam && fu && pad == 0 && !aligned16 && has_fused2(HP)) fam = 2;  // the two-roles kernel loads dwords into registers
+        if (!fam && fu && pad == 0 && !aligned16 && has_fused(HP)) fam = 1;   // so does the fused kernel
+        if (t2 && pad == 1 && has_tile2g_pad((int)HP)) fam = 6;
+      }
+      if (fam) {
+        TileBatch tb;
+        for (int i = 0; i < kTileItems; ++i) {
+          tb.x[i] = x + (long long)c_begin * strideC;
+          tb.out[i] = out;
+          tb.begin[i] = 0;
+        }
+        tb.begin[1] = tb.begin[kTileItems] = g.nmaps;
+        tb.map_elems = strideC;
+        tb.total = g.nmaps;
+        tb.count = 1;
+        return dispatch_tile_family(fam, (int)HP, tb, st);
+      }
+      if (algo != DCTS_ALGO_AUTO) return DCTS_E_UNSUPPORTED;
+    }
+    if (split_ok && algo != DCTS_ALGO_DIRECT) {
+      const SplitWs sws = split_ws(g.nmaps, (int)HP);
+      if (!workspace || workspace_bytes < sws.total) return DCTS_E_WORKSPACE;
+      if (reinterpret_cast<uintptr_t>(workspace) & 15) return DCTS_E_ALIGN;  // pass 2 stages the intermediate the same way
+      basis_forget_range(workspace, sws.total);
+      return dispatch_split((int)HP, g, out, workspace, st);
+    }
+  } else {
+    if (algo == DCTS_ALGO_SPLIT || algo == DCTS_ALGO_PIPE) return DCTS_E_UNSUPPORTED;
+    if (algo == DCTS_ALGO_FUSED || algo == DCTS_ALGO_TILE2D) {
+      // coefficients through the large-tile kernels themselves (leaf outputs + k_assemble): what the
+      // parity tests use to check that those kernels compute the DCT and not merely its energy
+      const bool dense = has_split(HP, WP) && pad == 0 && strideH == W && g.contiguous && strideC == H * W &&
+                         (reinterpret_cast<uintptr_t>(x + (long long)c_begin * strideC) & 15) == 0;
+      if (!dense) return DCTS_E_UNSUPPORTED;
+      const long long tile_bytes = (long long)HP * WP * 4;
+      const long long ws_maps = workspace ? (long long)(workspace_bytes / (size_t)tile_bytes) : 0;
+      if (ws_maps < 1 || (reinterpret_cast<uintptr_t>(workspace) & 15)) return DCTS_E_WORKSPACE;
+      const float* x0 = x + (long long)c_begin * strideC;
+      float* scratch = reinterpret_cast<float*>(workspace);
+      basis_forget_range(workspace, workspace_bytes);
+      if (algo == DCTS_ALGO_TILE2D)
+        return HP == 224 ? dispatch_tile2d_coeff((int)HP, x0, g.nmaps, out, scratch, ws_maps, st)
+                         : dispatch_tile2g_coeff((int)HP, x0, g.nmaps, out, scratch, ws_maps, st);
+      if (has_fused2(HP)) return dispatch_fused2_coeff((int)HP, x0, g.nmaps, out, scratch, ws_maps, st);
+      return dispatch_fused_coeff((int)HP, x0, g.nmaps, out, scratch, ws_maps, st);
+    }
+  }
+
+  const DirectWs ws = direct_ws(g.nmaps, (int)HP, (int)WP);
+  if (!workspace) return ws.total ? DCTS_E_WORKSPACE : DCTS_E_NULL;
+  if (workspace_bytes < ws.total) return DCTS_E_WORKSPACE;
+  char* wsp = reinterpret_cast<char*>(workspace);
+  float* CHt = reinterpret_cast<float*>(wsp + ws.off_ch);
+  float* CWt = reinterpret_cast<float*>(wsp + ws.off_cw);
+  float* T = reinterpret_cast<float*>(wsp + ws.off_t);
+  if (!cache_basis || !basis_cached(workspace, stream, (int)HP, (int)WP)) {
+    basis_forget_range(workspace, ws.total);  // whatever tables lay in the bytes this call uses are gone
+    hipLaunchKernelGGL(k_basis, dim3((unsigned)((HP * HP + 255) / 256)), dim3(256), 0, st, CHt, (int)HP);
+    hipLaunchKernelGGL(k_basis, dim3((unsigned)((WP * WP + 255) / 256)), dim3(256), 0, st, CWt, (int)WP);
+    if (cache_basis && hipGetLastError() == hipSuccess)
+      basis_remember(workspace, wsp + ws.off_ch, ws.off_t - ws.off_ch, stream, (int)HP, (int)WP);
+  } else {
+    basis_forget_range(wsp + ws.off_t, ws.total - ws.off_t);  // the T tiles may cover another entry's tables
+  }
+  hipLaunchKernelGGL((k_energy_direct<STORE>), dim3((unsigned)ws.grid), dim3(kDirectThreads), 0, st,
+                     g, pad, CHt, CWt, T, out);
+  return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+int dcts_version(void) { return DCTS_ABI_VERSION; }
+
+const char* dcts_strerror(int code) {
+  switch (code) {
+    case DCTS_OK: return "ok";
+    case DCTS_E_NULL: return "required pointer is NULL";
+    case DCTS_E_SHAPE: return "bad shape (N, C, H, W must be > 0 and tile edges <= 512)";
+    case DCTS_E_CHANNELS: return "channel slice outside [0, C_total)";
+    case DCTS_E_STRIDE: return "rows must be dense: strideW == 1 and strideH >= W";
+    case DCTS_E_WORKSPACE: return "workspace missing or smaller than dcts_workspace_bytes()";
+    case DCTS_E_UNSUPPORTED: return "no kernel of the requested family for this shape (rank: edges up to 64)";
+    case DCTS_E_ALIGN: return "pointer not 4-byte aligned (tensors) / 16-byte aligned (workspace)";
+    default: break;
+  }
+  if (code > 0) return hipGetErrorString((hipError_t)code);
+  return "unknown dctscore error";
+}
+
+size_t dcts_workspace_bytes(int64_t N, int64_t C_count, int64_t H, int64_t W) {
+  if (N <= 0 || C_count <= 0 || H <= 0 || W <= 0) return 0;
+  // worst case: odd front pad taken, direct kernel used
+  const int64_t HP = H + 1, WP = W + 1;
+  size_t need = direct_ws(N * C_count, (int)HP, (int)WP).total;
+  if (has_split(H, W)) {
+    const size_t s = split_ws(N * C_count, (int)H).total;
+    if (s > need) need = s;
+  }
+  return need;
+}
+
+int dcts_has_codelet(int64_t H, int64_t W) { return has_codelet(H, W) ? 1 : 0; }
+
+void dcts_workspace_invalidate(void* workspace) { basis_forget(workspace); }
+
+void dcts_workspace_invalidate_range(void* workspace, size_t bytes) {
+  basis_forget(workspace);
+  basis_forget_range(workspace, bytes);
+}
+
+int dcts_energy_f32_ex(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                       int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
+                       int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
+                       float* out_nc, void* workspace, size_t workspace_bytes, void* stream,
+                       int32_t algo) {
+  return run<false>(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count,
+                    pad_front_if_odd, out_nc, workspace, workspace_bytes, stream, algo);
+}
+
+int dcts_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                    int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
+                    int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd, float* out_nc,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+  return run<false>(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count,
+                    pad_front_if_odd, out_nc, workspace, workspace_bytes, stream, DCTS_ALGO_AUTO);
+}
+
+int dcts_dct2d_f32_ex(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                      int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
+                      int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
+                      float* out_coeff, void* workspace, size_t workspace_bytes, void* stream,
+                      int32_t algo) {
+  return run<true>(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count,
+                   pad_front_if_odd, out_coeff, workspace, workspace_bytes, stream, algo);
+}
+
+int dcts_dct2d_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                   int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
+                   int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd, float* out_coeff,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+  return run<true>(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count,
+                   pad_front_if_odd, out_coeff, workspace, workspace_bytes, stream, DCTS_ALGO_AUTO);
+}
+
+size_t dcts_weighted_workspace_bytes(int64_t N, int64_t C_count, int64_t H, int64_t W) {
+  if (N <= 0 || C_count <= 0 || H <= 0 || W <= 0) return 0;
+  // coefficients of a chunk of maps + what the coefficient path itself needs for that chunk
+  const int64_t HP = H + 1, WP = W + 1;
+  const long long tile = (long long)HP * WP * 4;
+  long long chunk = (256LL << 20) / tile;  // 256 MiB of coefficients per chunk at most
+  if (chunk < 1) chunk = 1;
+  if (chunk > N * C_count) chunk = N * C_count;
+  return align_up((size_t)(chunk * tile), 256) + align_up((size_t)(chunk * tile), 256) + dcts_workspace_bytes(N, C_count, H, W);
+}
+
+int dcts_weighted_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN,
+                             int64_t strideC, int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count,
+                             int32_t pad_front_if_odd, const float* weights, float* out_nc, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  if (!x || !out_nc || !weights) return DCTS_E_NULL;
+  if (N <= 0 || C_total <= 0 || H <= 0 || W <= 0) return DCTS_E_SHAPE;
+  if (c_count <= 0 || c_begin < 0 || (int64_t)c_begin + c_count > C_total) return DCTS_E_CHANNELS;
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15)) return workspace ? DCTS_E_ALIGN : DCTS_E_WORKSPACE;
+  const int pad = (pad_front_if_odd && (H % 2 != 0)) ? 1 : 0;
+  const int64_t HP = H + pad, WP = W + pad;
+  const long long tile = (long long)HP * WP * 4;
+  // workspace = [coefficients of a chunk][scratch the coefficient path may use]
+  const size_t inner_min = dcts_workspace_bytes(1, 1, H, W);
+  if (workspace_bytes < (size_t)(2 * tile) + inner_min) return DCTS_E_WORKSPACE;
+  long long chunk = (long long)((workspace_bytes - inner_min) / (size_t)(2 * tile));
+  if (chunk < 1) return DCTS_E_WORKSPACE;
+  const size_t off_inner = align_up((size_t)(chunk * tile), 256);
+  if (off_inner + (size_t)(chunk * tile) > workspace_bytes) --chunk;
+  if (chunk < 1) return DCTS_E_WORKSPACE;
+  char* wsp = reinterpret_cast<char*>(workspace);
+  float* coeff = reinterpret_cast<float*>(wsp);
+  void* inner = wsp + align_up((size_t)(chunk * tile), 256);
+  const size_t inner_bytes = workspace_bytes - align_up((size_t)(chunk * tile), 256);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // this call writes coefficients and scratch all over the workspace: no table cached in it survives, and the
+  // inner calls (interior pointer, offset depends on the tile shape) do not cache theirs
+  basis_forget(workspace);
+  basis_forget_range(workspace, workspace_bytes);
+  // the large-tile kernels where the tensor suits them, else whatever AUTO picks (codelet / direct)
+  // (every inner call covers channels of ONE sample, so the batch stride does not matter)
+  const bool dense = pad == 0 && H == W && strideH == W && strideW == 1 && strideC == H * W && (strideN * 4) % 16 == 0 &&
+                     (reinterpret_cast<uintptr_t>(x + (long long)c_begin * strideC) & 15) == 0;
+  const int algo = (dense && has_tile2d(HP)) ? DCTS_ALGO_TILE2D : (dense && (has_fused(HP) || has_fused2(HP))) ? DCTS_ALGO_FUSED : DCTS_ALGO_AUTO;
+  // maps are taken sample by sample in runs of channels so that a chunk is one strided view of x
+  const long long per_sample = c_count;
+  for (int64_t n = 0; n < N; ++n) {
+    for (long long c0 = 0; c0 < per_sample; c0 += chunk) {
+      const long long nc = (per_sample - c0) < chunk ? (per_sample - c0) : chunk;
+      int rc = run<true>(x + n * strideN, 1, C_total, H, W, strideN, strideC, strideH, strideW, (int32_t)(c_begin + c0), (int32_t)nc,
+                         pad_front_if_odd, coeff, inner, inner_bytes, stream, algo, /*cache_basis=*/false);
+      if (rc) return rc;
+      long long blocks = (nc * 64 + 255) / 256;
+      if (blocks > 4096) blocks = 4096;
+      hipLaunchKernelGGL(k_weighted_energy, dim3((unsigned)blocks), dim3(256), 0, st, coeff, weights, nc, (int)(HP * WP),
+                         out_nc + n * c_count + c0);
+      rc = (int)hipGetLastError();
+      if (rc) return rc;
+    }
+  }
+  return DCTS_OK;
+}
+
+int dcts_batch_sum_f32(const float* energy_nc, int64_t N, int64_t C_count, float* out_c,
+                       void* stream) {
+  if (!energy_nc || !out_c) return DCTS_E_NULL;
+  if (N <= 0 || C_count <= 0) return DCTS_E_SHAPE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_batch_sum, dim3((unsigned)((C_count + kSumCh - 1) / kSumCh)), dim3(kSumCh * kSumSl), 0, st,
+                     energy_nc, (long long)N, (long long)C_count, out_c);
+  return (int)hipGetLastError();
+}
+
+int dcts_running_mean_update_f32(const float* energy_nc, int64_t N, int64_t C_count,
+                                 float* feature_result, float total_before, void* stream) {
+  if (!energy_nc || !feature_result) return DCTS_E_NULL;
+  if (N <= 0 || C_count <= 0) return DCTS_E_SHAPE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_running_mean, dim3((unsigned)((C_count + kSumCh - 1) / kSumCh)), dim3(kSumCh * kSumSl), 0, st,
+                     energy_nc, (long long)N, (long long)C_count, feature_result, total_before);
+  return (int)hipGetLastError();
+}
+
+int dcts_energy_multi_f32(const dcts_tensor_item* items, int32_t count, int64_t H, int64_t W,
+                          int32_t pad_front_if_odd, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!items) return DCTS_E_NULL;
+  if (count <= 0 || H <= 0 || W <= 0) return DCTS_E_SHAPE;
+  const int pad = (pad_front_if_odd && (H % 2 != 0)) ? 1 : 0;
+  const int64_t HP = H + pad, WP = W + pad;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  for (int32_t i = 0; i < count; ++i) {
+    const dcts_tensor_item& t = items[i];
+    if (!t.x || !t.out_nc) return DCTS_E_NULL;
+    if (t.N <= 0 || t.C_total <= 0) return DCTS_E_SHAPE;
+    if (t.c_count <= 0 || t.c_begin < 0 || (int64_t)t.c_begin + t.c_count > t.C_total) return DCTS_E_CHANNELS;
+    if ((reinterpret_cast<uintptr_t>(t.x) & 3) || (reinterpret_cast<uintptr_t>(t.out_nc) & 3)) return DCTS_E_ALIGN;
+  }
+  if (has_codelet(HP, WP)) {
+    const int G = codelet_group_size((int)HP);
+    for (int32_t i0 = 0; i0 < count; i0 += kMultiItems) {
+      const int n = (count - i0) < kMultiItems ? (count - i0) : kMultiItems;
+      MultiGeom mg;
+      long long groups = 0;
+      for (int i = 0; i < n; ++i) {
+        const dcts_tensor_item& t = items[i0 + i];
+        MapGeom& g = mg.it[i].g;
+        g.x = t.x;
+        g.nmaps = t.N * (int64_t)t.c_count;
+        g.strideN = t.strideN;
+        g.strideC = t.strideC;
+        g.strideH = W;
+        g.c_count = t.c_count;
+        g.c_begin = t.c_begin;
+        g.H = (int)H;
+        g.W = (int)W;
+        g.contiguous = (t.N == 1 || t.strideN == (int64_t)t.c_count * t.strideC) ? 1 : 0;
+        mg.it[i].out = t.out_nc;
+        mg.it[i].group_begin = groups;
+        groups += (g.nmaps + G - 1) / G;
+      }
+      for (int i = n; i < kMultiItems; ++i) mg.it[i] = mg.it[0];
+      mg.total_groups = groups;
+      mg.count = n;
+      const int rc = dispatch_codelet_multi((int)HP, pad, mg, st);
+      if (rc) return rc;
+    }
+    return DCTS_OK;
+  }
+  // large tiles with a single-launch kernel: the dense tensors go into ONE launch per 32 of them (their
+  // maps form one index space: a CU that would get a fraction of a map from one small tensor now
+  // draws from all of them); results are those of one call per tensor, bit for bit
+  const int fam = (pad == 0 && H == W && has_split(HP, WP)) ? tile_family((int)HP, DCTS_ALGO_AUTO, 0)
+                  : ((pad == 1 && H == W && has_tile2g_pad((int)HP)) ? 6 : 0);
+  TileBatch tb;
+  int nb = 0;
+  auto flush = [&]() -> int {
+    if (!nb) return DCTS_OK;
+    for (int i = nb; i < kTileItems; ++i) {
+      tb.x[i] = tb.x[0];
+      tb.out[i] = tb.out[0];
+      tb.begin[i + 1] = tb.begin[nb];
+    }
+    tb.map_elems = H * W;
+    tb.total = tb.begin[nb];
+    tb.count = nb;
+    nb = 0;
+    return dispatch_tile_family(fam, (int)HP, tb, st);
+  };
+  for (int32_t i = 0; i < count; ++i) {
+    const dcts_tensor_item& t = items[i];
+    const float* x0 = t.x + (int64_t)t.c_begin * t.strideC;
+    // (the dword-loading kernels - tile2g, families 5 and 6, and the fused kernels, families 1 and 2 - take any 4-byte-aligned base, the others need 16)
+    const bool dense = fam && t.strideC == H * W && (t.N == 1 || t.strideN == (int64_t)t.c_count * t.strideC) &&
+                       ((reinterpret_cast<uintptr_t>(x0) & 15) == 0 || fam >= 5 || fam == 2 || fam == 1);
+    if (dense) {
+      if (nb == 0) tb.begin[0] = 0;
+      tb.x[nb] = x0;
+      tb.out[nb] = t.out_nc;
+      tb.begin[nb + 1] = tb.begin[nb] + t.N * (int64_t)t.c_count;
+      if (++nb == kTileItems) {
+        const int rc = flush();
+        if (rc) return rc;
+      }
+      continue;
+    }
+    // everything else: one call per tensor (split / direct), same stream
+    const int rc = run<false>(t.x, t.N, t.C_total, H, W, t.strideN, t.strideC, W, 1, t.c_begin, t.c_count,
+                              pad_front_if_odd, t.out_nc, workspace, workspace_bytes, stream, DCTS_ALGO_AUTO);
+    if (rc) return rc;
+  }
+  return flush();
+}
+
+int dcts_energy_mixed_f32(const dcts_shaped_item* items, int32_t count, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+  if (!items) return DCTS_E_NULL;
+  if (count <= 0) return DCTS_E_SHAPE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  for (int32_t i = 0; i < count; ++i) {
+    const dcts_tensor_item& t = items[i].t;
+    if (!t.x || !t.out_nc) return DCTS_E_NULL;
+    if (t.N <= 0 || t.C_total <= 0 || items[i].H <= 0 || items[i].W <= 0) return DCTS_E_SHAPE;
+    if (t.c_count <= 0 || t.c_begin < 0 || (int64_t)t.c_begin + t.c_count > t.C_total) return DCTS_E_CHANNELS;
+    if ((reinterpret_cast<uintptr_t>(t.x) & 3) || (reinterpret_cast<uintptr_t>(t.out_nc) & 3)) return DCTS_E_ALIGN;
+  }
+  auto eligible = [&](const dcts_shaped_item& it) {
+    return it.H == it.W && mixed_has((int)it.H) && !(it.pad_front_if_odd && (it.H % 2 != 0));
+  };
+  // 1. every small-tile tensor, whatever its shape, in one launch per kMixedItems of them
+  MixedGeom mg;
+  int n = 0;
+  long long groups = 0;
+  auto flush = [&]() -> int {
+    if (!n) return DCTS_OK;
+    for (int i = n; i < kMixedItems; ++i) mg.it[i] = mg.it[0];
+    mg.total_groups = groups;
+    mg.count = n;
+    n = 0;
+    groups = 0;
+    return dispatch_codelet_mixed(mg, st);
+  };
+  for (int32_t i = 0; i < count; ++i) {
+    if (!eligible(items[i])) continue;
+    const dcts_tensor_item& t = items[i].t;
+    MapGeom& g = mg.it[n].g;
+    g.x = t.x;
+    g.nmaps = t.N * (int64_t)t.c_count;
+    g.strideN = t.strideN;
+    g.strideC = t.strideC;
+    g.strideH = items[i].W;
+    g.c_count = t.c_count;
+    g.c_begin = t.c_begin;
+    g.H = (int)items[i].H;
+    g.W = (int)items[i].W;
+    g.contiguous = (t.N == 1 || t.strideN == (int64_t)t.c_count * t.strideC) ? 1 : 0;
+    mg.it[n].out = t.out_nc;
+    mg.it[n].group_begin = groups;
+    const int G = 64 / (int)items[i].H;
+    groups += (g.nmaps + G - 1) / G;
+    if (++n == kMixedItems) {
+      const int rc = flush();
+      if (rc) return rc;
+    }
+  }
+  int rc = flush();
+  if (rc) return rc;
+  // 2. the rest shape by shape (first occurrence order), through dcts_energy_multi_f32
+  dcts_tensor_item buf[64];
+  for (int32_t i = 0; i < count; ++i) {
+    if (eligible(items[i])) continue;
+    bool seen = false;
+    for (int32_t k = 0; k < i && !seen; ++k)
+      seen = !eligible(items[k]) && items[k].H == items[i].H && items[k].W == items[i].W &&
+             (items[k].pad_front_if_odd != 0) == (items[i].pad_front_if_odd != 0);
+    if (seen) continue;
+    int m = 0;
+    for (int32_t k = i; k < count; ++k) {
+      if (eligible(items[k]) || items[k].H != items[i].H || items[k].W != items[i].W ||
+          (items[k].pad_front_if_odd != 0) != (items[i].pad_front_if_odd != 0))
+        continue;
+      buf[m++] = items[k].t;
+      if (m == 64) {
+        rc = dcts_energy_multi_f32(buf, m, items[i].H, items[i].W, items[i].pad_front_if_odd, workspace, workspace_bytes, stream);
+        if (rc) return rc;
+        m = 0;
+      }
+    }
+    if (m) {
+      rc = dcts_energy_multi_f32(buf, m, items[i].H, items[i].W, items[i].pad_front_if_odd, workspace, workspace_bytes, stream);
+      if (rc) return rc;
+    }
+  }
+  return DCTS_OK;
+}
+
+int dcts_running_mean_update_multi_f32(const dcts_update_desc* descs, int32_t count, void* stream) {
+  if (!descs) return DCTS_E_NULL;
+  if (count <= 0) return DCTS_E_SHAPE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  for (int32_t i0 = 0; i0 < count; i0 += kMultiMax) {
+    const int n = (count - i0) < kMultiMax ? (count - i0) : kMultiMax;
+    UpdateBatch b;
+    int64_t cmax = 0;
+    for (int i = 0; i < n; ++i) {
+      b.d[i] = descs[i0 + i];
+      if (!b.d[i].energy_nc || !b.d[i].feature_result) return DCTS_E_NULL;
+      if (b.d[i].N <= 0 || b.d[i].C_count <= 0) return DCTS_E_SHAPE;
+      if (b.d[i].C_count > cmax) cmax = b.d[i].C_count;
+    }
+    for (int i = n; i < kMultiMax; ++i) b.d[i] = b.d[0];
+    hipLaunchKernelGGL(k_running_mean_multi, dim3((unsigned)((cmax + kSumCh - 1) / kSumCh), (unsigned)n),
+                       dim3(kSumCh * kSumSl), 0, st, b);
+  }
+  return (int)hipGetLastError();
+}
+
+#ifdef DCTS_FUSED_STAMPS
+int dcts_debug_fused_stamps(unsigned long long* host_out /*[16][16]*/, int reset) {
+  if (reset) {
+    static unsigned long long zeros[16][16] = {};
+    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_fused_stamps), zeros, sizeof(zeros));
+  }
+  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_fused_stamps), 16 * 16 * sizeof(unsigned long long));
+}
+#endif
+
+int dcts_debug_stream_read_f32(const float* x, int64_t n, float* sink, void* stream) {
+  if (!x || !sink) return DCTS_E_NULL;
+  if (n <= 0) return DCTS_E_SHAPE;
+  hipLaunchKernelGGL(k_calib_read, dim3(256 * 32), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x,
+                     (long long)n, sink);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -2,7 +2,7 @@
 //
 // One lane transforms a whole length-N vector held in its own VGPRs: no cross-lane
 // traffic, no LDS, every twiddle an instruction literal. The kernels in
-// dct_kernels.hip run one such codelet per lane along H, transpose the tile through
+// codelet.hip run one such codelet per lane along H, transpose the tile through
 // LDS, and run a second one along W.
 //
 // What is computed (the unnormalised DCT-II; the orthonormal scaling of

@@ -1,0 +1,170 @@
+// dcts_internal.h - what the translation units of libdctscore.so know of each other: the descriptor structs the kernels
+// take by value, the dispatchers of every kernel family (each defined in its family's unit), and the host-side shape
+// predicates and workspace sizes the C ABI (api.hip) needs without any kernel body.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include "codelet_sizes.h"
+
+namespace dctsi {
+
+struct MapGeom {
+  const float* x;
+  long long nmaps;    // N * c_count
+  long long strideN;  // elements
+  long long strideC;  // elements
+  long long strideH;  // elements (direct kernel only; codelet kernels require == W)
+  int c_count;
+  int c_begin;
+  int H, W;           // data dims (before the odd front pad)
+  int contiguous;     // 1: map m starts at x + c_begin*strideC + m*strideC (no div needed)
+};
+
+__device__ __forceinline__ const float* map_base(const MapGeom& g, long long m) {
+  if (g.contiguous) return g.x + (long long)g.c_begin * g.strideC + m * g.strideC;
+  const long long n = m / g.c_count;
+  const long long j = m - n * g.c_count;
+  return g.x + n * g.strideN + (g.c_begin + j) * g.strideC;
+}
+
+// Several hooked tensors of the same tile shape in ONE launch (single-sweep harness, bench): the
+// groups of all tensors form one index space; a wave walks it with a grid stride and tracks which
+// tensor its current group belongs to. CIFAR-sized layers are 5-20 us kernels when launched one
+// by one - the launch ramp and tail cost more than the work.
+constexpr int kMultiItems = 32;
+struct MultiItem {
+  MapGeom g;
+  float* out;
+  long long group_begin;  // first global group index of this tensor
+};
+struct MultiGeom {
+  MultiItem it[kMultiItems];
+  long long total_groups;
+  int count;
+};
+
+// Tensors of DIFFERENT small tile shapes in one launch (k_energy_codelet_mixed, codelet.hip)
+constexpr int kMixedItems = 48;
+struct MixedGeom {
+  MultiItem it[kMixedItems];
+  long long total_groups;
+  int count;
+};
+#define DCTS_MIXED_SIZES(X) X(2) X(4) X(8) X(16) X(32)
+constexpr bool mixed_has(int e) {
+#define DCTS_CASE(N) \
+  if (e == N) return true;
+  DCTS_MIXED_SIZES(DCTS_CASE)
+#undef DCTS_CASE
+  return false;
+}
+
+// Dense tensors of one large tile shape as ONE map index space (fused / pipelined kernels): map m of
+// the batch is map m - begin[t] of tensor t. U2-Net-p hooks ten 288x288 tensors of 16 or 64 channels;
+// launched one by one at batch 12 they give a CU 0.75 or 3 maps each, together 16.5.
+constexpr int kTileItems = 32;
+struct TileBatch {
+  const float* x[kTileItems];
+  float* out[kTileItems];
+  long long begin[kTileItems + 1];  // begin[count] = total
+  long long map_elems;              // floats per map (dense: maps of a tensor are adjacent)
+  long long total;
+  int count;
+};
+
+// compute units of the current device, queried once (256 on MI355X; the persistent grids are sized by it)
+inline int num_cus() {
+  static const int n = [] {
+    int dev = 0, cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu < 1)
+      cu = 256;
+    return cu;
+  }();
+  return n;
+}
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// ---- which shapes a family serves (from the tables of codelet_sizes.h) -----------------------------------------
+inline bool has_codelet(long long HP, long long WP) {
+  if (HP != WP) return false;
+#define DCTS_CASE(N) \
+  if (HP == N) return true;
+  DCTS_CODELET_SIZES(DCTS_CASE)
+#undef DCTS_CASE
+  return false;
+}
+
+constexpr bool has_lane_kernel(int n) { return n == 7 || n == 9; }
+
+inline bool has_split(long long HP, long long WP) {
+  if (HP != WP) return false;
+#define DCTS_CASE(N_, M_, L_) \
+  if (HP == N_) return true;
+  DCTS_SPLIT_TABLE(DCTS_CASE)
+#undef DCTS_CASE
+  return false;
+}
+
+inline bool has_fused(long long N) {
+#define DCTS_CASE(N_, M_, L_) \
+  if (N == N_) return true;
+  DCTS_FUSED_TABLE(DCTS_CASE)
+#undef DCTS_CASE
+  return false;
+}
+
+inline bool has_fused2(long long N) {
+#define DCTS_CASE(N_, M_, L_) \
+  if (N == N_) return true;
+  DCTS_FUSED2_TABLE(DCTS_CASE)
+#undef DCTS_CASE
+  return false;
+}
+
+inline bool has_pipe(long long N) {
+#define DCTS_CASE(N_, M_, L_) \
+  if (N == N_) return true;
+  DCTS_PIPE_TABLE(DCTS_CASE)
+#undef DCTS_CASE
+  return false;
+}
+
+// ---- codelet.hip: square tiles with both edges <= 64 ------------------------------------------------------------
+int codelet_group_size(int HP);  // maps per wave and iteration of the kernel that serves edge HP
+int dispatch_codelet(int store, int HP, int WP, int pad, const MapGeom& g, float* out, hipStream_t st);
+int dispatch_codelet_dma(int N, const MapGeom& g, float* out, hipStream_t st);
+int dispatch_codelet_multi(int HP, int pad, const MultiGeom& mg, hipStream_t st);
+int dispatch_lane(int n, const MultiGeom& mg, hipStream_t st);
+int dispatch_codelet_mixed(const MixedGeom& mg, hipStream_t st);
+
+// ---- split.hip, split_more.hip: two launches per chunk of maps, intermediate in the workspace ------------------
+struct SplitWs {
+  long long chunk_maps;
+  size_t off_t, off_part, total;
+};
+int split_partials_per_map(int N);
+SplitWs split_ws(long long nmaps, int N);
+int dispatch_split(int N, const MapGeom& g, float* out, void* workspace, hipStream_t st);
+int dispatch_split_more(int N, const MapGeom& g, float* out, void* workspace, hipStream_t st);  // the 8 * M entries added in round 3
+
+// ---- single-launch large-tile kernels: fused.hip, fused2.hip, pipe.hip, tile2d.hip, tile2g.hip -----------------
+int dispatch_fused(int N, const TileBatch& tb, hipStream_t st);
+int dispatch_fused2(int N, const TileBatch& tb, hipStream_t st);
+int dispatch_pipe(int N, const TileBatch& tb, hipStream_t st);
+int dispatch_tile2d(int N, const TileBatch& tb, hipStream_t st);
+// tile2g.hip: mid-size edges as a 2-D radix split with several maps per round
+int has_tile2g(int N);
+int has_tile2g_pad(int N);
+int dispatch_tile2g(int N, const TileBatch& tb, hipStream_t st);
+int dispatch_tile2g_pad(int N, const TileBatch& tb, hipStream_t st);  // tiles with the odd front pad (N = H + 1)
+// coefficient output through the large-tile kernels (debug / parity): leaf outputs into `scratch`
+// (scratch_maps tiles), then k_assemble
+int dispatch_fused_coeff(int N, const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps, hipStream_t st);
+int dispatch_fused2_coeff(int N, const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps, hipStream_t st);
+int dispatch_tile2d_coeff(int N, const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps, hipStream_t st);
+int dispatch_tile2g_coeff(int N, const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps, hipStream_t st);
+
+}  // namespace dctsi

@@ -1,4 +1,4 @@
-// rect.h - what dct_kernels.hip needs to know of rect.hip (non-square / non-dense-row tiles through the 1-D codelets)
+// rect.h - what api.hip needs to know of rect.hip (non-square / non-dense-row tiles through the 1-D codelets)
 #pragma once
 #include <hip/hip_runtime.h>
 

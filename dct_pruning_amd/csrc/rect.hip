@@ -1,5 +1,5 @@
 // rect.hip - tiles whose two edges both have a codelet (codelet_sizes.h) but that the square codelet kernels of
-// dct_kernels.hip do not take: NON-SQUARE maps (56 x 28, 14 x 20 ...: an --input_size that is not square) and maps
+// codelet.hip do not take: NON-SQUARE maps (56 x 28, 14 x 20 ...: an --input_size that is not square) and maps
 // whose rows are not dense (strideH > W: a spatial crop of a wider tensor).
 //
 // Replaces, for these shapes, the per-map loop of the reference hooks
@@ -10,7 +10,7 @@
 // ONE kernel for every (HP, WP) pair instead of 22 x 22 instantiations: the tile edges are kernel arguments (wave-
 // uniform, in SGPRs), and each of the two passes is a switch over the codelet sizes - a scalar branch to the straight-
 // line codelet of that length, so a wave executes exactly two of the 44 codelet bodies the kernel contains. Everything
-// else is the codelet kernel's scheme (dct_kernels.hip, codelet_group): a wave takes G = floor(64 / min(HP, WP)) maps per
+// else is the codelet kernel's scheme (codelet.hip, codelet_group): a wave takes G = floor(64 / min(HP, WP)) maps per
 // iteration (each pass in as many sub-steps as its lane count needs); pass 1: lane = column, HP strided loads (consecutive lanes = consecutive addresses), column codelet,
 // results into the wave's LDS slab; pass 2: lane = row, WP LDS reads, row codelet, squares, segmented shuffle sum over
 // the HP rows of a map. No workgroup barrier (the slab is private to the wave). Registers are those of the largest
@@ -240,7 +240,7 @@ int dispatch_rect(const RectGeom& g_in, float* out, int store_coeff, hipStream_t
   const size_t lds = (size_t)kRectWaves * g.G * g.map_lds * sizeof(float);
   const long long ngroups = (g.nmaps + g.G - 1) / g.G;
   long long blocks = (ngroups + kRectWaves - 1) / kRectWaves;
-  const long long cap = (long long)rect_num_cus() * 64;  // a grid several times the residency (dct_kernels.hip, GRID_WAVES_PER_CU)
+  const long long cap = (long long)rect_num_cus() * 64;  // a grid several times the residency (codelet.hip, GRID_WAVES_PER_CU)
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   static const hipError_t attr_rc = [] {  // four 64 x 65 slabs are 66.6 KB: above the 64 KB a kernel gets without asking

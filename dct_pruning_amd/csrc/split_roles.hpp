@@ -1,12 +1,14 @@
-// split_roles.hpp - pieces shared by the large-tile kernel families (dct_kernels.hip, tile2d.hip):
+// split_roles.hpp - pieces shared by the large-tile kernel families (split / fused / fused2 / pipe, tile2d.hip, tile2g.hip):
 // LDS pointer types, the multi-tensor map index space, the radix-2 role tree of the split DCT
 // (which M-point problem each of the 2^L roles solves, the in-place butterfly network that
 // produces the roles' inputs, its rotation constants) and a few wave-level helpers.
-// Every translation unit gets its own copy (anonymous namespace).
+// Every translation unit gets its own copy of the functions and tables (anonymous namespace); the TileBatch
+// descriptor itself is dctsi::TileBatch (dcts_internal.h), so that the dispatchers' prototypes can name it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <utility>
 #include "dct_codelets.hpp"
+#include "dcts_internal.h"
 
 namespace {
 
@@ -14,18 +16,8 @@ namespace {
 using lds_ptr = __attribute__((address_space(3))) float*;
 using lds_cptr = const __attribute__((address_space(3))) float*;
 
-// Dense tensors of one large tile shape as ONE map index space (fused / pipelined kernels): map m of
-// the batch is map m - begin[t] of tensor t. U2-Net-p hooks ten 288x288 tensors of 16 or 64 channels;
-// launched one by one at batch 12 they give a CU 0.75 or 3 maps each, together 16.5.
-constexpr int kTileItems = 32;
-struct TileBatch {
-  const float* x[kTileItems];
-  float* out[kTileItems];
-  long long begin[kTileItems + 1];  // begin[count] = total
-  long long map_elems;              // floats per map (dense: maps of a tensor are adjacent)
-  long long total;
-  int count;
-};
+using dctsi::kTileItems;
+using dctsi::TileBatch;
 // `hint`: the caller's map indices ascend (a persistent workgroup walks m, m + grid, ...), so the scan resumes where
 // the previous lookup of the same sequence ended instead of at tensor 0: every step is a dependent scalar load, and a
 // seven-tensor batch of 288 x 288 maps cost 4.7 % of the launch in these scans (three lookups per map).

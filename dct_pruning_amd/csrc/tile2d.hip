@@ -4,7 +4,7 @@
 // Replaces, for these tile shapes, the per-map loop of the reference hooks
 // (utils/common.py:262-277: dct.dct_2d(output[i,j,:,:], norm='ortho'), then sum(coeff^2)).
 //
-// Why another family. The split kernels of dct_kernels.hip transform one axis at a time: per axis
+// Why another family. The split kernels (split_kernels.hpp, fused.hip, pipe.hip) transform one axis at a time: per axis
 // the strip is staged in LDS, butterflied in place (read + write), read again by the M-point role
 // codelets, and dumped once more for the other axis: 3 LDS writes + 4 reads per point and five
 // workgroup barriers per 64-column step. tools/probes/valu_probe.hip shows what that costs on
@@ -37,13 +37,8 @@
 #include <stdint.h>
 
 #include "../../include/dctscore.h"
+#include "dcts_internal.h"  // dispatch_tile2d, dispatch_tile2d_coeff
 #include "split_roles.hpp"
-
-namespace dctsi {
-int dispatch_tile2d(int N, const void* tile_batch, hipStream_t st);
-int dispatch_tile2d_coeff(int N, const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps,
-                          hipStream_t st);
-}  // namespace dctsi
 
 namespace {
 
@@ -651,7 +646,7 @@ __device__ __forceinline__ void t2_load_seq(const float* __restrict__ in_b, unsi
 
 // piece `i` (64 lanes x 16 B) of the raw image: rows 0..N-1, columns [VB*M, N) of the map, dense
 // [row][RAWW] in LDS. Raw instruction (ordering is the kernel's own s_waitcnt vmcnt(0) + barrier;
-// see FusedStage::piece_raw in dct_kernels.hip for why not the builtin).
+// see FusedStage::piece_raw in pipe.hip for why not the builtin).
 template <int M>
 __device__ __forceinline__ void t2_dma_piece(const float* __restrict__ in_b, lds_ptr raw, int i, int lane) {
   using Cfg = T2Cfg<M>;
@@ -950,8 +945,7 @@ extern "C" int t2_dev_stamps(unsigned long long* host_out /*[16][16]*/, int rese
 #endif
 
 namespace dctsi {
-int dispatch_tile2d(int N, const void* tile_batch, hipStream_t st) {
-  const TileBatch& tb = *static_cast<const TileBatch*>(tile_batch);
+int dispatch_tile2d(int N, const TileBatch& tb, hipStream_t st) {
 #define DCTS_CASE(N_, M_) \
   case N_:                \
     return launch_tile2d<M_>(tb, st);

@@ -6,7 +6,7 @@
 // tile2d.hip does this for 224 x 224 (one map per round: 784 items of 8 x 8 mirrored samples fill 14 of the
 // 16 waves, two 28 x 28 leaf blocks per wave pass). The same structure at 144 x 144 has 324 items - five
 // waves busy in the network phase - and 18 x 18 leaf blocks that leave a wave pass a third full, which is why
-// the strip / park kernels of dct_kernels.hip (k_split_fused) kept these shapes at 0.31-0.42 of the HBM peak:
+// the strip / park kernels of fused.hip (k_split_fused) kept these shapes at 0.31-0.42 of the HBM peak:
 // three LDS writes + four reads per point and five workgroup barriers per 64-column strip.
 // Here a ROUND is G maps (G = floor(64 / M): 3 at 144, 4 at 128 and 112, 3 at 72 ...):
 //   - an item is (g, p, q): the 2^L x 2^L mirrored samples x[g][a*M + p~][b*M + q~]; one lane loads them
@@ -32,16 +32,8 @@
 #include <stdint.h>
 
 #include "../../include/dctscore.h"
+#include "dcts_internal.h"  // has_tile2g[_pad], dispatch_tile2g[_pad], dispatch_tile2g_coeff
 #include "split_roles.hpp"
-
-namespace dctsi {
-int dispatch_tile2g(int N, const void* tile_batch, hipStream_t st);
-int dispatch_tile2g_coeff(int N, const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps,
-                          hipStream_t st);
-int has_tile2g(int N);
-int has_tile2g_pad(int N);
-int dispatch_tile2g_pad(int N, const void* tile_batch, hipStream_t st);
-}  // namespace dctsi
 
 namespace {
 
@@ -933,8 +925,7 @@ int has_tile2g(int N) {
 #undef DCTS_CASE
   return 0;
 }
-int dispatch_tile2g(int N, const void* tile_batch, hipStream_t st) {
-  const TileBatch& tb = *static_cast<const TileBatch*>(tile_batch);
+int dispatch_tile2g(int N, const TileBatch& tb, hipStream_t st) {
 #define DCTS_CASE(N_, L_, M_, G_) \
   case N_:                        \
     return launch_tile2g<L_, M_, G_>(tb, st);
@@ -946,8 +937,7 @@ int dispatch_tile2g(int N, const void* tile_batch, hipStream_t st) {
 #undef DCTS_CASE
 }
 // odd front pad (tile edge N = H + 1 after the pad; the maps in memory are H x H, tb.map_elems = H * H): the AUTO shapes only
-int dispatch_tile2g_pad(int N, const void* tile_batch, hipStream_t st) {
-  const TileBatch& tb = *static_cast<const TileBatch*>(tile_batch);
+int dispatch_tile2g_pad(int N, const TileBatch& tb, hipStream_t st) {
 #define DCTS_CASE(N_, L_, M_, G_) \
   case N_:                        \
     return launch_tile2g<L_, M_, G_, 1>(tb, st);

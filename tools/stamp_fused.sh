@@ -10,7 +10,7 @@ if [ ! -f "$lib" ]; then
   mkdir -p gpurun_out/stamps
   lib=gpurun_out/stamps/libdctscore_stamps.so
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-pass-failed -Wno-inline-asm -fno-slp-vectorize -DDCTS_FUSED_STAMPS \
-    -o "$lib" dct_pruning_amd/csrc/dct_kernels.hip dct_pruning_amd/csrc/tile2d.hip
+    -o "$lib" dct_pruning_amd/csrc/all_units.hip dct_pruning_amd/csrc/tile2d.hip dct_pruning_amd/csrc/tile2g.hip dct_pruning_amd/csrc/rect.hip dct_pruning_amd/csrc/rank.hip
 fi
 export DCTS_STAMPS_LIB="$lib"
 python3 - "$edge" "$nmaps" <<'PY'

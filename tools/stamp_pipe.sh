@@ -7,7 +7,7 @@ edge=${1:-224}; nmaps=${2:-4096}
 if [ ! -f build_dev/libstamps.so ]; then
   mkdir -p build_dev
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-pass-failed -Wno-inline-asm -fno-slp-vectorize -DDCTS_DEV_FAST \
-    -DDCTS_FUSED_STAMPS -o build_dev/libstamps.so dct_pruning_amd/csrc/dct_kernels.hip
+    -DDCTS_FUSED_STAMPS -o build_dev/libstamps.so dct_pruning_amd/csrc/all_units.hip dct_pruning_amd/csrc/tile2d.hip dct_pruning_amd/csrc/tile2g.hip dct_pruning_amd/csrc/rect.hip dct_pruning_amd/csrc/rank.hip
 fi
 python3 - "$edge" "$nmaps" <<'PY'
 import ctypes, sys, torch
