@@ -5,7 +5,8 @@ DCT-II -> sum of squared coefficients -> per-channel running mean -> .npy score 
 (reference: utils/common.py:230-309 and :367-977). The arithmetic runs in hand-written
 gfx950 HIP kernels behind the C ABI of include/dctscore.h; this package is the host-side
 mirror of the reference's hook / imp_score interface. A second criterion, the HRank feature-map
-rank (rank_nc, imp_score(criterion="rank")), shares everything above the kernel.
+rank (rank_nc, imp_score(criterion="rank")), shares everything above the kernel, and so does a third, the per-band
+DCT energy spectrum (band_energy_nc, imp_score(criterion="bands"), bands.py: K frequency bands per map in one pass).
 """
 from .ops import (  # noqa: F401
     ALGO_AUTO,
@@ -18,14 +19,16 @@ from .ops import (  # noqa: F401
     ALGO_SPLIT,
     ALGO_TILE2D,
     ALGO_RECT,
+    band_energy_nc,
     batch_sum,
     dct2d,
     energy_mixed,
     energy_multi,
     energy_nc,
+    has_band_kernel,
     has_codelet,
     rank_nc,
     weighted_energy_nc,
 )
 
-__all__ = ["energy_nc", "energy_multi", "energy_mixed", "dct2d", "batch_sum", "has_codelet", "weighted_energy_nc", "rank_nc", "ALGO_AUTO", "ALGO_DIRECT", "ALGO_CODELET", "ALGO_SPLIT", "ALGO_PREFETCH", "ALGO_FUSED", "ALGO_PIPE", "ALGO_LANE", "ALGO_TILE2D", "ALGO_RECT"]
+__all__ = ["energy_nc", "energy_multi", "energy_mixed", "dct2d", "batch_sum", "has_codelet", "weighted_energy_nc", "rank_nc", "band_energy_nc", "has_band_kernel", "ALGO_AUTO", "ALGO_DIRECT", "ALGO_CODELET", "ALGO_SPLIT", "ALGO_PREFETCH", "ALGO_FUSED", "ALGO_PIPE", "ALGO_LANE", "ALGO_TILE2D", "ALGO_RECT"]

@@ -41,6 +41,10 @@ SIGNATURES = {
     "dcts_energy_mixed_f32": (ctypes.c_int, [_vp, _i32, _vp, _sz, _vp]),
     "dcts_running_mean_update_multi_f32": (ctypes.c_int, [_vp, _i32, _vp]),
     "dcts_rank_f32": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "dcts_band_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i32]),
+    "dcts_has_band_kernel": (ctypes.c_int, [_i64, _i64]),
+    "dcts_band_energy_f32": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                            _i32, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _vp, _i32]),
     "dcts_debug_stream_read_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
 }
 

@@ -7,7 +7,7 @@
 // 2-D DCT-II and the squared coefficients are reduced to one fp32 energy per map.
 //
 // The kernel families are units of their own (codelet.hip, split.hip, fused.hip, fused2.hip, pipe.hip, tile2d.hip,
-// tile2g.hip, rect.hip, rank.hip). Here:
+// tile2g.hip, rect.hip, rank.hip, band.hip). Here:
 //   k_energy_direct   any (H, W) <= DCTS_MAX_EDGE: separable cosine-matrix transform with
 //                     the basis block staged in LDS; intermediate tile in a caller-provided
 //                     workspace (L2-resident). O(H*W*(H+W)) flops per map: the correct
@@ -679,6 +679,123 @@ int dcts_weighted_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t
       hipLaunchKernelGGL(k_weighted_energy, dim3((unsigned)blocks), dim3(256), 0, st, coeff, weights, nc, (int)(HP * WP),
                          out_nc + n * c_count + c0);
       rc = (int)hipGetLastError();
+      if (rc) return rc;
+    }
+  }
+  return DCTS_OK;
+}
+
+// ---- K weighted energies per map (band.hip) ------------------------------------------------------------------------
+// Fallback workspace: [coefficients of a chunk of maps][what the coefficient path needs for that chunk: the direct
+// kernel's tables and T tiles, or leaf tiles of the large-tile kernels]. Both parts are at most align(chunk * tile).
+static long long band_fallback_chunk(size_t workspace_bytes, int HP, int WP) {
+  const size_t tile = (size_t)HP * WP * 4;
+  const size_t fixed = direct_ws(1, HP, WP).off_t + 512;
+  if (workspace_bytes < fixed + 2 * tile) return 0;
+  return (long long)((workspace_bytes - fixed) / (2 * tile));
+}
+
+size_t dcts_band_workspace_bytes(int64_t N, int64_t C_count, int64_t H, int64_t W, int32_t K) {
+  if (N <= 0 || C_count <= 0 || H <= 0 || W <= 0 || K < 1 || K > DCTS_BAND_MAX) return 0;
+  if (H + 1 > DCTS_MAX_EDGE + 1 || W + 1 > DCTS_MAX_EDGE + 1) return 0;
+  // worst case: odd front pad taken. Shapes the fused kernel serves meet the fallback only as row-pitched views.
+  const int HP = (int)H + 1, WP = (int)W + 1;
+  const long long tile = (long long)HP * WP * 4;
+  const long long cap = (HP <= 65 && WP <= 65) ? (16LL << 20) : (128LL << 20);  // bytes of coefficients per chunk
+  long long chunk = cap / tile;
+  if (chunk < 1) chunk = 1;
+  if (chunk > N * C_count) chunk = N * C_count;
+  const size_t fallback = direct_ws(1, HP, WP).off_t + 512 + 2 * (size_t)(chunk * tile);
+  const size_t table = band_table_bytes(HP, WP, K);
+  return align_up(fallback > table ? fallback : table, 256);
+}
+
+int dcts_has_band_kernel(int64_t H, int64_t W) { return has_codelet(H, W) ? 1 : 0; }
+
+int dcts_band_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN,
+                         int64_t strideC, int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count,
+                         int32_t pad_front_if_odd, const float* weights, int32_t K, float* out_nck, void* workspace,
+                         size_t workspace_bytes, void* stream, int32_t algo) {
+  if (!x || !out_nck || !weights) return DCTS_E_NULL;
+  if (N <= 0 || C_total <= 0 || H <= 0 || W <= 0) return DCTS_E_SHAPE;
+  if (K < 1 || K > DCTS_BAND_MAX) return DCTS_E_SHAPE;
+  if (c_count <= 0 || c_begin < 0 || (int64_t)c_begin + c_count > C_total) return DCTS_E_CHANNELS;
+  if (strideW != 1 || strideH < W) return DCTS_E_STRIDE;
+  if ((reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(out_nck) & 3) ||
+      (reinterpret_cast<uintptr_t>(weights) & 3))
+    return DCTS_E_ALIGN;
+  const int pad = (pad_front_if_odd && (H % 2 != 0)) ? 1 : 0;
+  const int64_t HP = H + pad, WP = W + pad;
+  if (HP > DCTS_MAX_EDGE || WP > DCTS_MAX_EDGE) return DCTS_E_SHAPE;
+  if (N * (int64_t)c_count >= (1LL << 40)) return DCTS_E_SHAPE;
+  if (algo != DCTS_ALGO_AUTO && algo != DCTS_ALGO_CODELET && algo != DCTS_ALGO_DIRECT) return DCTS_E_UNSUPPORTED;
+  const bool fused_ok = has_codelet(HP, WP) && strideH == W;
+  if (algo == DCTS_ALGO_CODELET && !fused_ok) return DCTS_E_UNSUPPORTED;
+  if (!workspace) return DCTS_E_WORKSPACE;
+  if (reinterpret_cast<uintptr_t>(workspace) & 15) return DCTS_E_ALIGN;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+
+  if (fused_ok && algo != DCTS_ALGO_DIRECT) {
+    const size_t table_bytes = band_table_bytes((int)HP, (int)WP, K);
+    if (workspace_bytes < table_bytes) return DCTS_E_WORKSPACE;
+    basis_forget_range(workspace, table_bytes);  // the table overwrites whatever basis tables lay there
+    MapGeom g;
+    g.x = x;
+    g.nmaps = N * (int64_t)c_count;
+    g.strideN = strideN;
+    g.strideC = strideC;
+    g.strideH = strideH;
+    g.c_count = c_count;
+    g.c_begin = c_begin;
+    g.H = (int)H;
+    g.W = (int)W;
+    g.contiguous = (N == 1 || strideN == (int64_t)c_count * strideC) ? 1 : 0;
+    return dispatch_band((int)HP, pad, g, weights, K, reinterpret_cast<float*>(workspace), out_nck, st);
+  }
+
+  // fallback: coefficients of a chunk of maps through the coefficient path, then one reduction that reads each
+  // coefficient once for all K bands
+  long long chunk = band_fallback_chunk(workspace_bytes, (int)HP, (int)WP);
+  if (chunk < 1) return DCTS_E_WORKSPACE;
+  const long long tile = (long long)HP * WP * 4;
+  char* wsp = reinterpret_cast<char*>(workspace);
+  float* coeff = reinterpret_cast<float*>(wsp);
+  const size_t off_inner = align_up((size_t)(chunk * tile), 256);
+  void* inner = wsp + off_inner;
+  const size_t inner_bytes = workspace_bytes - off_inner;
+  // this call writes coefficients and scratch all over the workspace: no table cached in it survives, and the inner
+  // calls (interior pointer) do not cache theirs
+  basis_forget(workspace);
+  basis_forget_range(workspace, workspace_bytes);
+  // the large-tile kernels' own coefficient path where the tensor suits them, else whatever AUTO picks
+  const bool contiguous = N == 1 || strideN == (int64_t)c_count * strideC;
+  const bool dense = pad == 0 && H == W && strideH == W && strideC == H * W && (strideN * 4) % 16 == 0 &&
+                     (reinterpret_cast<uintptr_t>(x + (long long)c_begin * strideC) & 15) == 0;
+  const int inner_algo = (dense && has_tile2d(HP)) ? DCTS_ALGO_TILE2D
+                         : (dense && (has_fused(HP) || has_fused2(HP))) ? DCTS_ALGO_FUSED : DCTS_ALGO_AUTO;
+  const int hw = (int)(HP * WP);
+  if (chunk >= c_count && (contiguous || inner_algo == DCTS_ALGO_AUTO)) {
+    // whole samples per chunk: (n, channel) jointly, one strided view of x per call
+    const int64_t ns = chunk / c_count;
+    for (int64_t n0 = 0; n0 < N; n0 += ns) {
+      const int64_t nn = (N - n0) < ns ? (N - n0) : ns;
+      int rc = run<true>(x + n0 * strideN, nn, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count,
+                         pad_front_if_odd, coeff, inner, inner_bytes, stream, inner_algo, /*cache_basis=*/false);
+      if (rc) return rc;
+      rc = launch_band_reduce(coeff, weights, nn * c_count, hw, K, out_nck + n0 * c_count * K, st);
+      if (rc) return rc;
+    }
+    return DCTS_OK;
+  }
+  if (chunk > c_count) chunk = c_count;
+  for (int64_t n = 0; n < N; ++n) {
+    for (long long c0 = 0; c0 < c_count; c0 += chunk) {
+      const long long nc = (c_count - c0) < chunk ? (c_count - c0) : chunk;
+      int rc = run<true>(x + n * strideN, 1, C_total, H, W, strideN, strideC, strideH, strideW, (int32_t)(c_begin + c0),
+                         (int32_t)nc, pad_front_if_odd, coeff, inner, inner_bytes, stream, inner_algo,
+                         /*cache_basis=*/false);
+      if (rc) return rc;
+      rc = launch_band_reduce(coeff, weights, nc, hw, K, out_nck + (n * c_count + c0) * K, st);
       if (rc) return rc;
     }
   }

@@ -140,6 +140,14 @@ int dispatch_codelet_multi(int HP, int pad, const MultiGeom& mg, hipStream_t st)
 int dispatch_lane(int n, const MultiGeom& mg, hipStream_t st);
 int dispatch_codelet_mixed(const MixedGeom& mg, hipStream_t st);
 
+// ---- band.hip: K weighted energies per map (dcts_band_energy_f32) ------------------------------------------------
+int band_kb(int K);                                // K rounded up to 1, 2, 4, 8: the fused kernel's accumulator count
+size_t band_table_bytes(int HP, int WP, int K);    // the re-laid weight table T[l][u][KB] at the head of the workspace
+// fused kernel for square tiles with a codelet (HP after the odd pad): builds the table from `weights`, then one launch
+int dispatch_band(int HP, int pad, const MapGeom& g, const float* weights, int K, float* table, float* out, hipStream_t st);
+// fallback reduction: out[m][b] = sum_i weights[b][i] * coeff[m][i]^2 over `nmaps` dense tiles of `hw` coefficients
+int launch_band_reduce(const float* coeff, const float* weights, long long nmaps, int hw, int K, float* out, hipStream_t st);
+
 // ---- split.hip, split_more.hip: two launches per chunk of maps, intermediate in the workspace ------------------
 struct SplitWs {
   long long chunk_maps;

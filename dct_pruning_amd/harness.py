@@ -25,21 +25,41 @@ Additions (opt-in, results identical on fixed batches):
   criterion="rank"    HRank's score instead of the DCT energy: the numerical rank of every map
                       (dcts_rank_f32, ops.rank_nc) through the same hooks, accumulators, schedules and
                       sharding; files go to rank_conv/<net>_limit<L>/rank_*.npy (hooks
-                      get_feature_hook_rank / get_feature_hook_densenet_rank).
+                      get_feature_hook_rank / get_feature_hook_densenet_rank);
+  criterion="bands"   the DCT energy split into K frequency bands (bands.partition; dcts_band_energy_f32,
+                      ops.band_energy_nc: all K bands in one pass over the map): a [C, K] spectrum per hook point in
+                      band_score/<net>_limit<L>_<kind><K>/band_*.npy, which bands.collapse turns into imp_*.npy for
+                      any band weighting afterwards, on the host (hooks get_feature_hook_bands /
+                      get_feature_hook_densenet_bands / get_feature_hook_u2net_input_bands).
 """
 import os
 
 import numpy as np
 import torch
 
+from . import bands as _bands
 from . import ops, schedules, sharding
 from .accumulate import DeviceAccumulator, DeviceBatchAccumulator, HostAccumulator
 
 # tests swap these for the oracle to exercise the host logic without a GPU
 _energy_nc = ops.energy_nc
 _rank_nc = ops.rank_nc
+_band_energy_nc = ops.band_energy_nc
 
-CRITERIA = ("dct", "rank")
+CRITERIA = ("dct", "rank", "bands")
+
+# the band criterion's partition (K, kind): imp_score(criterion="bands", bands=...) sets it for its hooks
+_band_cfg = (4, "square")
+_band_weight_cache = {}
+
+
+def _band_weights(H, W, device):
+    """The one-hot [K, H, W] partition of the current band configuration on `device` (H, W after the odd pad)."""
+    key = (H, W, str(device)) + tuple(_band_cfg)
+    w = _band_weight_cache.get(key)
+    if w is None:
+        w = _band_weight_cache[key] = torch.from_numpy(_bands.partition(H, W, *_band_cfg)).to(device)
+    return w
 
 # the reference's module globals (utils/common.py:258-259)
 _acc = HostAccumulator()
@@ -69,7 +89,25 @@ def _hook_rank(kind, x):
     return _rank_nc(x)
 
 
+def _band_piece(x, c_begin, c_count, pad):
+    """[N, c_count, K] band energies of a channel range of x (pad: the cv2 path's odd front pad)."""
+    H, W = x.shape[2], x.shape[3]
+    p = 1 if (pad and H % 2 == 1) else 0
+    return _band_energy_nc(x, _band_weights(H + p, W + p, x.device), c_begin=c_begin, c_count=c_count,
+                           pad_front_if_odd=bool(pad))
+
+
+def _hook_bands(kind, x):
+    """The K band energies of every map the DCT hook of that kind scores (same channels, same odd pad): [N, c, K]."""
+    b = x.shape[1]
+    if kind == "last12":
+        return _band_piece(x, b - 12, 12, True)
+    return _band_piece(x, 0, b, kind == "input")
+
+
 def _hook_score(criterion, kind, x):
+    if criterion == "bands":
+        return _hook_bands(kind, x)
     return _hook_rank(kind, x) if criterion == "rank" else _hook_energy(kind, x)
 
 
@@ -115,6 +153,24 @@ def get_feature_hook_densenet_rank(self, input, output):
     _acc.update(_hook_rank("last12", output))
 
 
+def get_feature_hook_bands(self, input, output):
+    """get_feature_hook with the energy split into K bands: the accumulator's view(a, -1).sum(0) runs over the flat
+    [a, C*K] view, so feature_result is the [C, K] spectrum in row-major order."""
+    _acc.update(_hook_bands("full", output))
+
+
+def get_feature_hook_densenet_bands(self, input, output):
+    """channels [b-12, b), cv2 path (odd front pad)."""
+    _acc.update(_hook_bands("last12", output))
+
+
+def get_feature_hook_u2net_input_bands(self, input, output):
+    """scores input[0], cv2 path (odd front pad)."""
+    _acc.update(_hook_bands("input", input[0]))
+
+
+_BAND_HOOKS = {"full": get_feature_hook_bands, "last12": get_feature_hook_densenet_bands,
+               "input": get_feature_hook_u2net_input_bands}
 _HOOKS = {"full": get_feature_hook, "last12": get_feature_hook_densenet, "input": get_feature_hook_u2net_input}
 _RANK_HOOKS = {"full": get_feature_hook_rank, "last12": get_feature_hook_densenet_rank}
 
@@ -184,6 +240,8 @@ def _file_stem(criterion, stem):
     """rank files: the schedule's stem with the leading imp_ replaced by rank_ (imp_conv3 -> rank_conv3)."""
     if criterion == "rank" and stem.startswith("imp_"):
         return "rank_" + stem[len("imp_"):]
+    if criterion == "bands":  # imp_conv3 -> band_conv3; U2-Net-p's net.<module path> -> band_net.<module path>
+        return "band_" + (stem[len("imp_"):] if stem.startswith("imp_") else stem)
     return stem
 
 
@@ -211,6 +269,7 @@ class _PointHook:
         self.criterion = criterion
         self.batch, self.key, self.deferred = batch, key, deferred
         self.ranges, self.nominal_c, self.accs = ranges, nominal_c, {}
+        self.width = None  # K of the band criterion: scores come back as [c, K]
 
     def _pieces(self, x):
         """(key, c_begin, c_count, pad_front_if_odd) of every operator call this hook makes on x."""
@@ -240,8 +299,13 @@ class _PointHook:
                 e = _hook_score(self.criterion, self.kind, x)
             elif self.criterion == "rank":
                 e = _rank_nc(x, c_begin=cb, c_count=cc)
+            elif self.criterion == "bands":
+                e = _band_piece(x, cb, cc, pad)
             else:
                 e = _energy_nc(x, c_begin=cb, c_count=cc, pad_front_if_odd=pad)
+            if e.dim() == 3:  # [N, c, K] band energies: the accumulators see the dense [N, c*K] view
+                self.width = e.shape[2]
+                e = e.reshape(e.shape[0], -1)
             if self.batch is not None:
                 self.batch.add(key, e)
                 continue
@@ -254,28 +318,41 @@ class _PointHook:
     def scores(self, key=None):
         key = self.key if key is None else key
         if self.batch is not None:
-            return np.ascontiguousarray(self.batch.scores(key), dtype=np.float32)
-        return np.ascontiguousarray(self.accs[key].scores(), dtype=np.float32)
+            flat = np.ascontiguousarray(self.batch.scores(key), dtype=np.float32)
+        else:
+            flat = np.ascontiguousarray(self.accs[key].scores(), dtype=np.float32)
+        return flat if self.width is None else flat.reshape(-1, self.width)
 
 
 def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host", group=None, deferred=False,
-              criterion="dct"):
+              criterion="dct", bands=(4, "square")):
     """Counterpart of utils/common.py:367-977. `args` needs .net, .limit (and whatever
     load_data reads when train_loader is None). criterion="rank" scores HRank's feature-map rank instead of the
-    DCT energy and writes rank_conv/<net>_limit<L>/rank_*.npy."""
-    global _acc
+    DCT energy and writes rank_conv/<net>_limit<L>/rank_*.npy. criterion="bands" with bands=(K, kind) writes the
+    [C, K] band spectrum of every hook point to band_score/<net>_limit<L>_<kind><K>/band_*.npy."""
+    global _acc, _band_cfg
     if criterion not in CRITERIA:
         raise ValueError("imp_score: unknown criterion %r (expected one of %s)" % (criterion, ", ".join(CRITERIA)))
     if criterion == "rank" and deferred:
         raise ValueError("imp_score: criterion='rank' has no deferred mode; use single_sweep / accumulate instead")
     if criterion == "rank" and args.net == "u2netp":
         raise ValueError("imp_score: criterion='rank' supports edges up to 64; u2netp (up to 288) is out of scope")
+    if criterion == "bands":
+        if deferred:
+            raise ValueError("imp_score: criterion='bands' has no deferred mode; use single_sweep / accumulate instead")
+        K, kind = int(bands[0]), bands[1]
+        if not 1 <= K <= _bands.BAND_MAX or kind not in _bands.KINDS:
+            raise ValueError("imp_score: bands=(K, kind) needs 1 <= K <= %d and kind in %s, got %r"
+                             % (_bands.BAND_MAX, _bands.KINDS, (bands,)))
+        _band_cfg = (K, kind)
     if not hasattr(args, "limit"):
         # utils/load_models.py:819 calls imp_score from prune_*.py whose parsers define no --limit
         # (AttributeError in the reference as shipped); fall back to importance_generation.py's default
         args.limit = 5
-    root = "rank_conv" if criterion == "rank" else "importance_score"
+    root = {"rank": "rank_conv", "bands": "band_score"}.get(criterion, "importance_score")
     out_dir = root + "/" + args.net + "_limit" + str(args.limit)
+    if criterion == "bands":
+        out_dir += "_%s%d" % (_band_cfg[1], _band_cfg[0])
     world, rank = 1, 0
     if group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
         world = torch.distributed.get_world_size(group)
@@ -359,10 +436,13 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
                 handler.remove()
                 results[k] = hook.scores()
             else:
-                handler = layer.register_forward_hook((_RANK_HOOKS if criterion == "rank" else _HOOKS)[pt.kind])
+                table = {"rank": _RANK_HOOKS, "bands": _BAND_HOOKS}.get(criterion, _HOOKS)
+                handler = layer.register_forward_hook(table[pt.kind])
                 sweep(net, train_loader, args.limit)
                 handler.remove()
                 results[k] = np.ascontiguousarray(_acc.feature_result.numpy(), dtype=np.float32)
+                if criterion == "bands":
+                    results[k] = results[k].reshape(-1, _band_cfg[0])
                 _acc.reset()
             if world == 1:
                 _save(out_dir, args.net, pt, results[k], criterion)
@@ -371,7 +451,8 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
             return
 
     if world > 1:
-        layer_scores = _gather_results(results, units, len(pts), owner, world, rank, dev, group)
+        layer_scores = _gather_results(results, units, len(pts), owner, world, rank, dev, group,
+                                       width=_band_cfg[0] if criterion == "bands" else 1)
     else:
         layer_scores = {units[k].layer: results[k] for k in mine}
     if rank == 0:
@@ -384,10 +465,11 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
         torch.distributed.barrier(group)
 
 
-def _gather_results(local, units, n_layers, owner, world, rank, dev, group):
+def _gather_results(local, units, n_layers, owner, world, rank, dev, group, width=1):
     """One all-gather of the flat, equally padded score buffer (plus a tiny all-reduce that tells every rank
     the channel counts of the units, which only their owners know for certain: imp_score also runs on
-    already-pruned nets whose widths differ from the schedule's). Returns {layer: (C,) scores}."""
+    already-pruned nets whose widths differ from the schedule's). Returns {layer: (C,) scores}. width > 1 (the band
+    criterion's K): a unit of c channels carries c * width floats and the scores come back as (C, width)."""
     import torch.distributed as dist
     backend = dist.get_backend(group)
     cdev = dev if backend == "nccl" else torch.device("cpu")
@@ -412,10 +494,15 @@ def _gather_results(local, units, n_layers, owner, world, rank, dev, group):
     chans = [0] * n_layers
     for u in real:
         chans[u.layer] = max(chans[u.layer], u.c_hi)
+    if width > 1:
+        real = [sharding.Unit(u.layer, u.c_lo * width, u.c_hi * width, u.cost) for u in real]
+        chans = [c * width for c in chans]
     off, seg = sharding.layout(real, owner, world)
     flat = torch.zeros(seg, dtype=torch.float32, device=cdev)
     for k, v in local.items():
-        flat[off[k]:off[k] + counts[k]] = torch.from_numpy(v).to(cdev)
+        flat[off[k]:off[k] + counts[k] * width] = torch.from_numpy(v.reshape(-1)).to(cdev)
     gathered = sharding.all_gather_scores(flat, world, group)
     res = sharding.unpack(gathered, real, owner, off, chans)
+    if width > 1:
+        return {i: r.cpu().numpy().reshape(-1, width) for i, r in enumerate(res)}
     return {i: r.cpu().numpy() for i, r in enumerate(res)}

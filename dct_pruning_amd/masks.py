@@ -53,8 +53,13 @@ def score_files(score_dir):
     return sorted((f for f in os.listdir(score_dir) if f.endswith(".npy")), key=_natural)
 
 
-def masks_for_dir(score_dir, rates):
-    """{file stem: kept indices (int64, sorted)}; `rates` is a float or a list in natural file order."""
+class BandWeightsError(ValueError):
+    """A [C, K] band spectrum met without band weights, or with the wrong number of them."""
+
+
+def masks_for_dir(score_dir, rates, band_weights=None):
+    """{file stem: kept indices (int64, sorted)}; `rates` is a float or a list in natural file order. A 2-D score file
+    (a [C, K] band spectrum of imp_score(criterion="bands")) needs `band_weights` (K numbers): imp = file @ weights."""
     files = score_files(score_dir)
     if isinstance(rates, (int, float)):
         rates = [float(rates)] * len(files)
@@ -63,6 +68,15 @@ def masks_for_dir(score_dir, rates):
     out = {}
     for f, r in zip(files, rates):
         imp = np.load(os.path.join(score_dir, f), allow_pickle=False)
+        if imp.ndim == 2:
+            if band_weights is None:
+                raise BandWeightsError("%s holds a [%d, %d] band spectrum: give --band_weights w0,w1,... (one per band) to "
+                                 "turn it into scores" % (f, imp.shape[0], imp.shape[1]))
+            from .bands import apply_band_weights
+            try:
+                imp = apply_band_weights(imp, band_weights)
+            except ValueError as exc:
+                raise BandWeightsError("%s: %s" % (f, exc))
         c = imp.shape[0]
         out[f[:-4]] = select_index(imp, c, int(c * (1 - r)))
     return out
@@ -81,15 +95,27 @@ def main(argv=None):
     ap.add_argument("--compress_rate", default="[0.5]*200", help="reference DSL, e.g. '[0.50]*7+[0.95]*5'")
     ap.add_argument("--out", default=None, help="write the masks to this .npz")
     ap.add_argument("--compare", default=None, help="second score directory: report whether the masks match")
+    ap.add_argument("--band_weights", default=None,
+                    help="for directories of [C, K] band spectra (band_*.npy): one weight per band, e.g. 1,0.5,0.25,0")
     args = ap.parse_args(argv)
     rates = parse_compress_rate(args.compress_rate)
-    masks = masks_for_dir(args.imp_score, rates)
+    bw = None
+    if args.band_weights is not None:
+        from .bands import parse_band_weights
+        try:
+            bw = parse_band_weights(args.band_weights)
+        except ValueError as exc:
+            ap.error(str(exc))
+    try:
+        masks = masks_for_dir(args.imp_score, rates, bw)
+    except BandWeightsError as exc:
+        ap.error(str(exc))
     for k, v in masks.items():
         print("%s: keep %d" % (k, v.size))
     if args.out:
         np.savez(args.out, **masks)
     if args.compare:
-        bad = compare(masks, masks_for_dir(args.compare, rates))
+        bad = compare(masks, masks_for_dir(args.compare, rates, bw))
         print("masks identical" if not bad else "masks differ in: " + ", ".join(bad))
         return 1 if bad else 0
     return 0

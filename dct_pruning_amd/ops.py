@@ -200,6 +200,39 @@ def weighted_energy_nc(x, weights, c_begin=0, c_count=None, pad_front_if_odd=Fal
     return out
 
 
+def has_band_kernel(H, W):
+    """True if the fused band kernel takes an (H, W) tile (sizes after the odd pad)."""
+    return bool(_lib.load().dcts_has_band_kernel(H, W))
+
+
+def band_energy_nc(x, weights, c_begin=0, c_count=None, pad_front_if_odd=False, algo=ALGO_AUTO):
+    """K weighted energies per map in one pass: E[n, j, b] = sum_{u,v} weights[b,u,v] * dct_2d(x[n, c_begin+j])[u,v]**2
+    -> [N, c_count, K] fp32. `weights`: [K, H', W'] fp32 on x's device, K = 1 ... 8 (H' = H + 1 for an odd H with
+    pad_front_if_odd); one-hot weights (bands.partition) give the energy of K frequency bands.
+    algo: ALGO_AUTO (fused kernel where it exists, else the fallback), ALGO_CODELET (fused only), ALGO_DIRECT
+    (fallback only). Enqueues on the current stream of x's device; no synchronisation."""
+    _check_input(x)
+    c_begin, c_count = _slice(x, c_begin, c_count)
+    N, C, H, W = x.shape
+    pad = 1 if (pad_front_if_odd and H % 2 == 1) else 0
+    if (not isinstance(weights, torch.Tensor) or weights.dim() != 3 or tuple(weights.shape[1:]) != (H + pad, W + pad)
+            or weights.dtype != torch.float32 or weights.device != x.device):
+        raise ValueError("weights must be a float32 [K, %d, %d] tensor on %s" % (H + pad, W + pad, x.device))
+    K = weights.shape[0]
+    if x.stride(3) != 1 or x.stride(2) < W:
+        x = x.contiguous()
+    weights = weights.contiguous()
+    lib = _lib.load()
+    out = torch.empty((N, c_count, K), dtype=torch.float32, device=x.device)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    ws = _workspace(x.device, stream, max(lib.dcts_band_workspace_bytes(N, c_count, H, W, K), 16))
+    with torch.cuda.device(x.device):
+        _lib.check(lib.dcts_band_energy_f32(
+            x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3), c_begin, c_count,
+            1 if pad_front_if_odd else 0, weights.data_ptr(), K, out.data_ptr(), ws.data_ptr(), ws.numel(), stream, algo))
+    return out
+
+
 def rank_nc(x, c_begin=0, c_count=None, out=None):
     """R[n, j] = numerical rank of x[n, c_begin+j] -> [N, c_count] fp32 (exact integers; all-zero map: +0.0).
 

@@ -9,7 +9,10 @@ in libdctscore (HIP, gfx950); a GPU is required.
 Extra, opt-in flags: --synthetic (seeded synthetic batches; also lifts the need for a
 checkpoint), --input_size, --seed, --single_sweep, --device_accumulate, --deferred, --criterion {dct,rank}
 (rank: HRank's feature-map rank instead of the DCT energy, written to rank_conv/<net>_limit<L>/rank_*.npy;
-edges up to 64, so not with --net u2netp, and not with --deferred). Multi-GPU: launch with
+edges up to 64, so not with --net u2netp, and not with --deferred; bands: the DCT energy of K frequency bands per
+channel, --bands K --band_kind {square,diag}, a [C, K] spectrum per hook point under
+band_score/<net>_limit<L>_<kind><K>/band_*.npy that `python -m dct_pruning_amd.bands` collapses into imp_*.npy for any
+band weighting; not with --deferred). Multi-GPU: launch with
 `python -m torch.distributed.run --nproc-per-node G importance_generation.py ...` — hook points
 are sharded over the ranks and rank 0 writes the files.
 """
@@ -41,13 +44,21 @@ def parse_args(argv=None):
     parser.add_argument("--device_accumulate", action="store_true", help="keep the running mean on the GPU")
     parser.add_argument("--deferred", action="store_true",
                         help="single sweep, one scoring launch per tile shape per batch (implies the two above)")
-    parser.add_argument("--criterion", type=str, default="dct", choices=("dct", "rank"),
-                        help="dct: DCT energy (importance_score/); rank: HRank feature-map rank (rank_conv/)")
+    parser.add_argument("--criterion", type=str, default="dct", choices=("dct", "rank", "bands"),
+                        help="dct: DCT energy (importance_score/); rank: HRank feature-map rank (rank_conv/); "
+                             "bands: DCT energy per frequency band (band_score/)")
+    parser.add_argument("--bands", type=int, default=4, help="--criterion bands: number of bands K, 1 ... 8")
+    parser.add_argument("--band_kind", type=str, default="square", choices=("square", "diag"),
+                        help="--criterion bands: L-infinity shells (square) or anti-diagonal stripes (diag)")
     args = parser.parse_args(argv)
     if args.criterion == "rank" and args.net == "u2netp":
         parser.error("--criterion rank supports feature maps up to 64 x 64; --net u2netp is out of its scope")
     if args.criterion == "rank" and args.deferred:
         parser.error("--criterion rank has no --deferred mode (use --single_sweep / --device_accumulate)")
+    if args.criterion == "bands" and args.deferred:
+        parser.error("--criterion bands has no --deferred mode (use --single_sweep / --device_accumulate)")
+    if args.criterion == "bands" and not 1 <= args.bands <= 8:
+        parser.error("--bands must be between 1 and 8")
     return args
 
 
@@ -100,7 +111,7 @@ def main(argv=None):
 
     harness.imp_score(net, args, single_sweep=args.single_sweep,
                       accumulate="device" if args.device_accumulate else "host", deferred=args.deferred,
-                      criterion=args.criterion)
+                      criterion=args.criterion, bands=(args.bands, args.band_kind))
     if world > 1:
         torch.distributed.destroy_process_group()
 

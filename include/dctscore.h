@@ -43,7 +43,9 @@ extern "C" {
 
 /* 2: workspace contract (the library may leave basis tables in a workspace between calls; 16-byte
  *    alignment; dcts_workspace_invalidate[_range]), multi / mixed / weighted entry points.
- * 3: dcts_rank_f32 (the HRank criterion) and DCTS_RANK_MAX_EDGE. */
+ * 3: dcts_rank_f32 (the HRank criterion) and DCTS_RANK_MAX_EDGE. The band entry points (dcts_band_energy_f32,
+ *    dcts_band_workspace_bytes, dcts_has_band_kernel, DCTS_BAND_MAX) were added to 3 WITHOUT a bump: they are purely
+ *    additive, and a library that lacks them fails at symbol lookup. */
 #define DCTS_ABI_VERSION 3
 
 enum {
@@ -177,6 +179,38 @@ int dcts_weighted_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t
                              int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
                              const float* weights, float* out_nc, void* workspace, size_t workspace_bytes,
                              void* stream);
+
+/*
+ * K weighted energies per map in ONE pass over the data (band.hip). With c = dct_2d(x[n, c_begin+j], norm='ortho')
+ * (H' x W' after the optional odd front pad) and `weights` a dense [K, H', W'] fp32 device array:
+ *
+ *     out_nck[(n*c_count + j)*K + b] = sum_{u,v} weights[b, u, v] * c[u, v]^2        [N, c_count, K] fp32, dense
+ *
+ * One-hot weights make that the energy of K frequency bands (dct_pruning_amd/bands.py builds the partitions); all
+ * ones with K = 1 is dcts_energy_f32 up to rounding, K = 1 in general is dcts_weighted_energy_f32's score.
+ *   K          1 ... DCTS_BAND_MAX, else DCTS_E_SHAPE. Weights are arbitrary floats.
+ *   x, strides, c_begin, c_count, pad_front_if_odd    as for dcts_energy_f32; any (H, W) <= DCTS_MAX_EDGE.
+ *   algo       DCTS_ALGO_AUTO     the fused kernel where it exists (square tiles with a codelet,
+ *                                 dcts_has_band_kernel(H', W') == 1, rows dense: strideH == W), else the fallback;
+ *              DCTS_ALGO_CODELET  the fused kernel only (DCTS_E_UNSUPPORTED otherwise);
+ *              DCTS_ALGO_DIRECT   the fallback only: coefficients of a chunk of maps through the coefficient path
+ *                                 (dcts_dct2d_f32_ex's kernels) into the workspace, then one reduction that reads
+ *                                 each coefficient once for all K bands.
+ *   workspace  >= dcts_band_workspace_bytes(N, c_count, H, W, K) bytes, 16-byte aligned, never NULL. The fused kernel
+ *              keeps the re-laid weight table (at most 128 KiB) at its head; the fallback chunks by what it is given.
+ * A map's K values depend on nothing but that map and the weights (not on N, the channel slice, K's rounding, the
+ * other maps or the launch count): bit-reproducible, no atomics. An all-zero map gives +0.0 in every band (finite
+ * weights); a NaN / Inf map affects only its own K outputs. Only enqueues on `stream`.
+ */
+#define DCTS_BAND_MAX 8
+size_t dcts_band_workspace_bytes(int64_t N, int64_t C_count, int64_t H, int64_t W, int32_t K);
+/* 1 if the fused band kernel takes an (H, W) tile (sizes AFTER the odd pad). */
+int dcts_has_band_kernel(int64_t H, int64_t W);
+int dcts_band_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                         int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
+                         int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
+                         const float* weights, int32_t K, float* out_nck, void* workspace, size_t workspace_bytes,
+                         void* stream, int32_t algo);
 
 /*
  * Fused batch reduction for benchmarking and for the single-sweep harness:
