@@ -1,5 +1,6 @@
-// api.hip - the C ABI of include/dctscore.h: argument validation, the choice of a kernel family for a shape, the typed
-// dispatch into the family units (dcts_internal.h, rect.h), and the kernels that belong to no family.
+// api.hip - the C ABI of include/dctscore.h. Every entry point turns its arguments into a TensorView, validate() checks it,
+// choose() names the kernel family that serves it (the only place where a shape becomes a family), and run() packs that family's
+// descriptor and calls its dispatcher (dcts_internal.h, rect.h). Also the kernels that belong to no family.
 //
 // Replaces the per-map Python loop of the reference hooks (utils/common.py:262-309):
 //   c = [dct.dct_2d(output[i,j,:,:], norm='ortho') ...]; torch.sum(dct.mul(dct)).item()
@@ -15,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <mutex>
 
 #include "../../include/dctscore.h"
@@ -280,57 +282,198 @@ DirectWs direct_ws(long long nmaps, int HP, int WP) {
   return w;
 }
 
-// dense, 16-byte aligned, even-edge square tiles take the prefetching kernel
-bool dma_ok(int HP, int WP, int pad, const MapGeom& g) {
-  if (pad || HP != WP || (HP % 2) != 0) return false;
-  if (!g.contiguous || g.strideC != (long long)HP * WP) return false;
-  return (reinterpret_cast<uintptr_t>(g.x + (long long)g.c_begin * g.strideC) & 15) == 0;
-}
+// ---- one tensor argument set ------------------------------------------------------------------------------------------
+// What an entry point is given for one tensor, and the facts every path derives from it. The derived facts are
+// functions: the weighted and band fallbacks re-aim a view at a run of channels of one sample, and nothing goes stale.
+struct TensorView {
+  const float* x;
+  int64_t N, C_total, H, W, strideN, strideC, strideH, strideW;  // strides in elements
+  int32_t c_begin, c_count;
+  bool pad_front_if_odd;
 
-bool has_tile2d(long long N) { return N == 224 || has_tile2g((int)N) != 0; }
+  int pad() const { return (pad_front_if_odd && (H % 2 != 0)) ? 1 : 0; }  // the test is on H only, the pad on both axes
+  int64_t HP() const { return H + pad(); }
+  int64_t WP() const { return W + pad(); }
+  int64_t nmaps() const { return N * (int64_t)c_count; }
+  bool contiguous() const { return N == 1 || strideN == (int64_t)c_count * strideC; }  // map m starts at base() + m * strideC
+  const float* base() const { return x + (long long)c_begin * strideC; }
+  bool aligned16() const { return (reinterpret_cast<uintptr_t>(base()) & 15) == 0; }
+  bool dense_rows() const { return strideW == 1 && strideH == W; }
+  bool dense_square() const { return H == W && dense_rows() && strideC == H * W; }  // every map one dense H x H block
+  bool dense_maps() const { return dense_square() && contiguous(); }                // and the blocks adjacent: an array of tiles
+};
 
-// Does AUTO take the several-maps-per-round 2-D split (tile2g.hip, family 5) for `nmaps` maps of edge HP? Same box,
-// % of the HBM peak, fused / pipelined kernel -> tile2g: 72: 30.9 -> 44.1 (9645 maps), 29.7 -> 45.1 (32768); 80: 33.2 ->
-// 40.3, 32.9 -> 37.6; 144: 30.1 -> 33.7 (2411), 32.0 -> 42.4 (4992), 31.8 -> 41.0 (8192); 160: 31.2 -> 34.1 (1953), 33.5 ->
-// 37.3 (4096); 128: 45.1 -> 43.3 (3051) but 44.1 -> 50.6 (8192); 112: 38.8 -> 34.6, 39.8 -> 38.2
-// (profiles/r03_tile2g_vs_fused_same_box.txt). The choice must not depend on the map count: dcts_energy_multi_f32
-// promises the bits of one call per tensor, whatever the tensors' sizes. So 72, 80, 144, 160 take it, 112 and 128
-// keep the fused / pipelined kernels (DCTS_ALGO_TILE2D still selects it for them).
-bool tile2g_auto(int HP, long long /*nmaps*/) {
-  return has_tile2g(HP) && HP != 96 && HP != 112 && HP != 128;
+// the list entry points: rows are dense by contract
+TensorView view_of(const dcts_tensor_item& t, int64_t H, int64_t W, int32_t pad_front_if_odd) {
+  return TensorView{t.x, t.N, t.C_total, H, W, t.strideN, t.strideC, W, 1, t.c_begin, t.c_count, pad_front_if_odd != 0};
 }
+TensorView view_of(const dcts_shaped_item& it) { return view_of(it.t, it.H, it.W, it.pad_front_if_odd); }
 
-// which single-launch large-tile kernel serves an edge: 0 none, 1 fused, 2 fused with two roles per
-// wave, 3 pipelined (AUTO order: pipelined, two-roles, fused)
-int tile_family(int HP, int algo, long long nmaps) {
-  if (algo == DCTS_ALGO_TILE2D) return HP == 224 ? 4 : (has_tile2g(HP) ? 5 : 0);
-  if (algo == DCTS_ALGO_AUTO && tile2g_auto(HP, nmaps)) return 5;
-  // AUTO order: 2-D split (tile2d.hip), pipelined, two-roles, fused. 224: 2-D split 33-42 % of the HBM
-  // peak against 31-37 % pipelined, same box, 996...16384 maps
-  if (algo == DCTS_ALGO_AUTO && HP == 224) return 4;
-  if (algo == DCTS_ALGO_PIPE) return has_pipe(HP) && has_fused(HP) ? 3 : 0;
-  if (algo == DCTS_ALGO_AUTO && has_pipe(HP) && has_fused(HP)) return 3;
-  if (has_fused2(HP)) return 2;  // AUTO uses the two-roles-per-wave fused kernel where it exists (288: 31 % vs 18 %, 320: 31 % vs 17 % of the HBM peak)
-  if (has_fused(HP)) return 1;
-  return 0;
-}
-int dispatch_tile_family(int fam, int HP, const TileBatch& tb, hipStream_t st) {
-  switch (fam) {
-    case 6:
-      return dispatch_tile2g_pad(HP, tb, st);
-    case 5:
-      return dispatch_tile2g(HP, tb, st);
-    case 4:
-      return dispatch_tile2d(HP, tb, st);
-    case 3:
-      return dispatch_pipe(HP, tb, st);
-    case 2:
-      return dispatch_fused2(HP, tb, st);
-    case 1:
-      return dispatch_fused(HP, tb, st);
-    default:
-      return DCTS_E_UNSUPPORTED;
+// The argument checks, in the one order every entry point makes them in. `ptrs`: the other device pointers the call requires
+// (out, weights), tested for NULL and 4-byte alignment together with x. `shape_ok`: the entry point's own shape condition (the
+// band count). The entry points differ only in where they stop:
+//   Channels  dcts_weighted_energy_f32: its workspace comes next; the first inner coefficient call checks the rest (so a bad
+//             workspace is reported before a bad stride);
+//   Align     the list entry points, per item: an edge beyond DCTS_MAX_EDGE or 2^40 maps is found by the per-tensor call;
+//   All       everything else.
+enum class Checks { Channels, Align, All };
+int validate(const TensorView& v, std::initializer_list<const void*> ptrs, Checks upto, bool shape_ok = true) {
+  bool null = !v.x, misaligned = (reinterpret_cast<uintptr_t>(v.x) & 3) != 0;
+  for (const void* p : ptrs) {
+    null = null || !p;
+    misaligned = misaligned || (reinterpret_cast<uintptr_t>(p) & 3) != 0;
   }
+  if (null) return DCTS_E_NULL;
+  if (v.N <= 0 || v.C_total <= 0 || v.H <= 0 || v.W <= 0 || !shape_ok) return DCTS_E_SHAPE;
+  if (v.c_count <= 0 || v.c_begin < 0 || (int64_t)v.c_begin + v.c_count > v.C_total) return DCTS_E_CHANNELS;
+  if (upto == Checks::Channels) return DCTS_OK;
+  if (v.strideW != 1 || v.strideH < v.W) return DCTS_E_STRIDE;
+  if (misaligned) return DCTS_E_ALIGN;
+  if (upto == Checks::Align) return DCTS_OK;
+  if (v.HP() > DCTS_MAX_EDGE || v.WP() > DCTS_MAX_EDGE) return DCTS_E_SHAPE;
+  if (v.nmaps() >= (1LL << 40)) return DCTS_E_SHAPE;
+  return DCTS_OK;
+}
+
+// (aggregates in the field order of dcts_internal.h / rect.h; rect.hip fills in the launch parameters left zero here)
+MapGeom map_geom(const TensorView& v) {
+  return MapGeom{v.x, v.nmaps(), v.strideN, v.strideC, v.strideH, v.c_count, v.c_begin, (int)v.H, (int)v.W, v.contiguous() ? 1 : 0};
+}
+RectGeom rect_geom(const TensorView& v) {
+  RectGeom r{v.x, v.nmaps(), v.strideN, v.strideC, v.strideH, v.c_count, v.c_begin, (int)v.H, (int)v.W, (int)v.HP(), (int)v.WP(), v.pad()};
+  r.contiguous = v.contiguous() ? 1 : 0;
+  return r;
+}
+
+// ---- how a shape finds its kernel (DESIGN.md, section of that name) -----------------------------------------------
+// Every way a call can be served. Direct is api.hip's own cosine-matrix kernel, the others are units of their own.
+enum class Family { Direct, Codelet, Lane, CodeletDma, Rect, Split, Fused, Fused2, Pipe, Tile2d, Tile2g, Tile2gPad };
+struct FamilyTraits {
+  int (*batch)(int, const TileBatch&, hipStream_t);  // its dispatcher if it takes a TileBatch: dense tensors of one shape as one map index space
+  bool base16;  // stages with 16-byte direct-to-LDS loads: the first map must lie on a 16-byte boundary (tile2g.hip gathers single
+                // dwords, the fused kernels load dwords into registers: any 4-byte-aligned base)
+  bool coeff;   // can store coefficients (the large-tile kernels: leaf outputs + k_assemble, 16-byte base then)
+};
+constexpr FamilyTraits kTraits[] = {
+    /* Direct     */ {nullptr, false, true},
+    /* Codelet    */ {nullptr, false, true},
+    /* Lane       */ {nullptr, false, false},
+    /* CodeletDma */ {nullptr, true, false},
+    /* Rect       */ {nullptr, false, true},
+    /* Split      */ {nullptr, true, false},
+    /* Fused      */ {dispatch_fused, false, true},
+    /* Fused2     */ {dispatch_fused2, false, true},
+    /* Pipe       */ {dispatch_pipe, true, false},
+    /* Tile2d     */ {dispatch_tile2d, true, true},
+    /* Tile2g     */ {dispatch_tile2g, false, true},
+    /* Tile2gPad  */ {dispatch_tile2g_pad, false, false},
+};
+static_assert(sizeof kTraits / sizeof kTraits[0] == (size_t)Family::Tile2gPad + 1, "one row per Family, in its order");
+constexpr FamilyTraits traits(Family f) { return kTraits[(int)f]; }
+
+// the single-launch large-tile families in the order AUTO tries them, each with the explicit request that names it; below,
+// which edges each serves
+constexpr struct { Family fam; int algo; } kTileOrder[] = {{Family::Tile2g, DCTS_ALGO_TILE2D}, {Family::Tile2d, DCTS_ALGO_TILE2D},
+    {Family::Pipe, DCTS_ALGO_PIPE}, {Family::Fused2, DCTS_ALGO_FUSED}, {Family::Fused, DCTS_ALGO_FUSED}};
+bool serves(Family f, int HP) {
+  switch (f) {
+    case Family::Tile2g: return has_tile2g(HP) != 0;
+    case Family::Tile2d: return HP == 224;
+    case Family::Pipe: return has_pipe(HP) && has_fused(HP);
+    case Family::Fused2: return has_fused2(HP);
+    case Family::Fused: return has_fused(HP);
+    default: return false;
+  }
+}
+// Edges tile2g.hip has but AUTO leaves to the fused / pipelined kernels. Same box, % of the HBM peak, fused / pipelined kernel ->
+// tile2g: 72: 30.9 -> 44.1 (9645 maps), 29.7 -> 45.1 (32768); 80: 33.2 -> 40.3, 32.9 -> 37.6; 144: 30.1 -> 33.7 (2411), 32.0 ->
+// 42.4 (4992), 31.8 -> 41.0 (8192); 160: 31.2 -> 34.1 (1953), 33.5 -> 37.3 (4096); 128: 45.1 -> 43.3 (3051) but 44.1 -> 50.6
+// (8192); 112: 38.8 -> 34.6, 39.8 -> 38.2 (profiles/r03_tile2g_vs_fused_same_box.txt). The choice must not depend on the map
+// count: dcts_energy_multi_f32 promises the bits of one call per tensor, whatever the tensors' sizes. So 72, 80, 144, 160 take
+// tile2g, 96, 112 and 128 keep the fused / pipelined kernels (DCTS_ALGO_TILE2D still selects it for them).
+constexpr bool tile2g_loses(int HP) { return HP == 96 || HP == 112 || HP == 128; }
+
+struct Choice { Family fam; int err; };  // err: DCTS_OK, or DCTS_E_UNSUPPORTED: the requested family has no kernel for this tensor
+constexpr Choice kUnsupported{Family::Direct, DCTS_E_UNSUPPORTED};
+
+// The family that serves a validated tensor: the whole policy, nothing launched, no workspace or memo touched. `aligned16`
+// is v.aligned16() for a call of its own; dcts_energy_multi_f32 asks what the tensor would take on a 16-byte base.
+Choice choose(const TensorView& v, int algo, bool store, bool aligned16) {
+  if (algo < DCTS_ALGO_AUTO || algo > DCTS_ALGO_RECT) return kUnsupported;
+  const int HP = (int)v.HP(), WP = (int)v.WP(), pad = v.pad();
+  auto can = [&](Family f) { return !store || traits(f).coeff; };
+
+  // 1. small tiles. Both edges have a 1-D codelet, but the maps are not square or their rows not dense: the run-time pair of
+  // codelets (rect.hip). Square dense-row maps keep their own kernels unless ALGO_RECT asks (tests compare the two).
+  const bool codelet_ok = has_codelet(HP, WP) && v.dense_rows();
+  const bool lane_ok = codelet_ok && can(Family::Lane) && pad == 0 && has_lane_kernel(HP);
+  const bool rect_ok = HP <= 64 && WP <= 64 && has_rect(HP, WP) != 0;
+  if ((algo == DCTS_ALGO_CODELET || algo == DCTS_ALGO_PREFETCH) && !codelet_ok) return kUnsupported;
+  if (algo == DCTS_ALGO_LANE && !lane_ok) return kUnsupported;
+  if (algo == DCTS_ALGO_RECT && !rect_ok) return kUnsupported;
+  if (rect_ok && (algo == DCTS_ALGO_RECT || (algo == DCTS_ALGO_AUTO && !codelet_ok))) return {Family::Rect, DCTS_OK};
+  if (codelet_ok && algo != DCTS_ALGO_DIRECT) {  // (a request for a large-tile family is served by the codelet kernel too)
+    if (lane_ok && (algo == DCTS_ALGO_AUTO || algo == DCTS_ALGO_LANE)) return {Family::Lane, DCTS_OK};
+    // the prefetching variant is opt-in: on MI355X it measured equal to the register-load kernel in steady state (both at the
+    // practical HBM rate) and ~2 % slower on the bench. Dense, 16-byte aligned, even-edge unpadded tiles only.
+    if (algo == DCTS_ALGO_PREFETCH) {
+      const bool dma_ok = can(Family::CodeletDma) && pad == 0 && HP % 2 == 0 && v.dense_maps() && aligned16;
+      return dma_ok ? Choice{Family::CodeletDma, DCTS_OK} : kUnsupported;
+    }
+    return {Family::Codelet, DCTS_OK};
+  }
+
+  // 2. large tiles: arrays of dense unpadded square tiles of a split-table edge
+  const bool tile_shape = has_split(HP, WP) && pad == 0 && v.dense_maps();
+  if (store) {
+    // coefficients through the large-tile kernels themselves, on request only: the parity tests check with them that those kernels
+    // compute the DCT and not merely its energy. (An edge of the split table that the family lacks is refused by its dispatcher.)
+    if (algo == DCTS_ALGO_SPLIT || algo == DCTS_ALGO_PIPE) return kUnsupported;  // neither family stores coefficients
+    if (algo == DCTS_ALGO_TILE2D || algo == DCTS_ALGO_FUSED) {
+      if (!tile_shape || !aligned16) return kUnsupported;
+      if (algo == DCTS_ALGO_TILE2D) return {HP == 224 ? Family::Tile2d : Family::Tile2g, DCTS_OK};
+      return {has_fused2(HP) ? Family::Fused2 : Family::Fused, DCTS_OK};
+    }
+    return {Family::Direct, DCTS_OK};
+  }
+  const bool split_ok = tile_shape && aligned16;  // pass 2 stages the intermediate as pass 1 stages the maps
+  if (algo == DCTS_ALGO_SPLIT && !split_ok) return kUnsupported;
+  if (algo == DCTS_ALGO_AUTO || algo == DCTS_ALGO_FUSED || algo == DCTS_ALGO_PIPE || algo == DCTS_ALGO_TILE2D) {
+    // AUTO order: several-maps-per-round 2-D split (tile2g.hip), 2-D split (tile2d.hip; 224: 33-42 % of the HBM peak against
+    // 31-37 % pipelined, same box, 996...16384 maps), pipelined, two roles per wave (288: 31 % vs 18 %, 320: 31 % vs 17 % of the
+    // HBM peak for the fused kernel), fused
+    if (tile_shape)
+      for (const auto& t : kTileOrder) {
+        const Family f = t.fam;
+        if ((algo != DCTS_ALGO_AUTO && algo != t.algo) || !serves(f, HP)) continue;
+        if (!aligned16 && traits(f).base16) continue;
+        // (kept as found, DESIGN.md: the measured exception holds on a 16-byte base only, so a 4-byte base takes tile2g at 96, 112, 128)
+        if (f == Family::Tile2g && algo == DCTS_ALGO_AUTO && aligned16 && tile2g_loses(HP)) continue;
+        return {f, DCTS_OK};
+      }
+    // 71 / 79 / 143 / 159 with the odd front pad (the cv2 path on odd maps): tile2g.hip pads while it gathers
+    if (pad == 1 && v.dense_maps() && (algo == DCTS_ALGO_AUTO || algo == DCTS_ALGO_TILE2D) && has_tile2g_pad(HP))
+      return {Family::Tile2gPad, DCTS_OK};
+    if (algo != DCTS_ALGO_AUTO) return kUnsupported;
+  }
+  // 3. two launches with the intermediate in the workspace, else the cosine-matrix kernel
+  if (split_ok && algo != DCTS_ALGO_DIRECT) return {Family::Split, DCTS_OK};
+  return {Family::Direct, DCTS_OK};
+}
+
+// one tensor as a batch of one
+TileBatch single_batch(const TensorView& v, float* out) {
+  TileBatch tb;
+  for (int i = 0; i < kTileItems; ++i) {
+    tb.x[i] = v.base();
+    tb.out[i] = out;
+    tb.begin[i] = 0;
+  }
+  tb.begin[1] = tb.begin[kTileItems] = v.nmaps();
+  tb.map_elems = v.strideC;
+  tb.total = v.nmaps();
+  tb.count = 1;
+  return tb;
 }
 
 // The direct kernel's basis tables live at the head of the caller's workspace. They are built once per
@@ -384,165 +527,104 @@ void basis_remember(void* ws, const void* tables, size_t table_bytes, void* stre
   g_basis_next = (g_basis_next + 1) % kBasisSlots;
 }
 
-template <bool STORE>
-int run(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN,
-        int64_t strideC, int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count,
-        int32_t pad_front_if_odd, float* out, void* workspace, size_t workspace_bytes,
-        void* stream, int32_t algo, bool cache_basis = true) {
-  if (!x || !out) return DCTS_E_NULL;
-  if (N <= 0 || C_total <= 0 || H <= 0 || W <= 0) return DCTS_E_SHAPE;
-  if (c_count <= 0 || c_begin < 0 || (int64_t)c_begin + c_count > C_total) return DCTS_E_CHANNELS;
-  if (strideW != 1 || strideH < W) return DCTS_E_STRIDE;
-  if ((reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(out) & 3)) return DCTS_E_ALIGN;
-  const int pad = (pad_front_if_odd && (H % 2 != 0)) ? 1 : 0;
-  const int64_t HP = H + pad, WP = W + pad;
-  if (HP > DCTS_MAX_EDGE || WP > DCTS_MAX_EDGE) return DCTS_E_SHAPE;
-  if (N * (int64_t)c_count >= (1LL << 40)) return DCTS_E_SHAPE;
-
-  MapGeom g;
-  g.x = x;
-  g.nmaps = N * (int64_t)c_count;
-  g.strideN = strideN;
-  g.strideC = strideC;
-  g.strideH = strideH;
-  g.c_count = c_count;
-  g.c_begin = c_begin;
-  g.H = (int)H;
-  g.W = (int)W;
-  g.contiguous = (N == 1 || strideN == (int64_t)c_count * strideC) ? 1 : 0;
+// One tensor, energies (out is [N, c_count]) or coefficients (store: out is [N, c_count, H', W']): validate -> choose -> launch.
+int run(bool store, const TensorView& v, float* out, void* workspace, size_t workspace_bytes, void* stream, int32_t algo,
+        bool cache_basis = true) {
+  if (const int rc = validate(v, {out}, Checks::All)) return rc;
+  const Choice c = choose(v, algo, store, v.aligned16());
+  if (c.err) return c.err;
+  const int HP = (int)v.HP(), WP = (int)v.WP(), pad = v.pad();
+  const MapGeom g = map_geom(v);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-
-  const bool codelet_ok = has_codelet(HP, WP) && strideH == W;
-  if ((algo == DCTS_ALGO_CODELET || algo == DCTS_ALGO_PREFETCH) && !codelet_ok) return DCTS_E_UNSUPPORTED;
-  if (algo != DCTS_ALGO_AUTO && algo != DCTS_ALGO_DIRECT && algo != DCTS_ALGO_CODELET &&
-      algo != DCTS_ALGO_SPLIT && algo != DCTS_ALGO_PREFETCH && algo != DCTS_ALGO_FUSED && algo != DCTS_ALGO_PIPE && algo != DCTS_ALGO_LANE && algo != DCTS_ALGO_TILE2D && algo != DCTS_ALGO_RECT)
-    return DCTS_E_UNSUPPORTED;
-  if (algo == DCTS_ALGO_LANE && !(codelet_ok && !STORE && pad == 0 && has_lane_kernel((int)HP))) return DCTS_E_UNSUPPORTED;
-  // both edges have a 1-D codelet, but the maps are not square or their rows not dense: the run-time pair of codelets
-  // (rect.hip). Square dense maps keep their own kernels unless ALGO_RECT asks (tests compare the two).
-  const bool rect_ok = HP <= 64 && WP <= 64 && has_rect((int)HP, (int)WP) != 0;
-  if (algo == DCTS_ALGO_RECT && !rect_ok) return DCTS_E_UNSUPPORTED;
-  if (rect_ok && (algo == DCTS_ALGO_RECT || (algo == DCTS_ALGO_AUTO && !codelet_ok))) {
-    RectGeom r{};
-    r.x = x;
-    r.nmaps = g.nmaps;
-    r.strideN = strideN;
-    r.strideC = strideC;
-    r.strideH = strideH;
-    r.c_count = c_count;
-    r.c_begin = c_begin;
-    r.H = (int)H;
-    r.W = (int)W;
-    r.HP = (int)HP;
-    r.WP = (int)WP;
-    r.pad = pad;
-    r.contiguous = g.contiguous;
-    return dispatch_rect(r, out, STORE ? 1 : 0, st);
-  }
-  if (codelet_ok && algo != DCTS_ALGO_DIRECT) {
-    if constexpr (!STORE) {
-      if ((algo == DCTS_ALGO_AUTO || algo == DCTS_ALGO_LANE) && pad == 0 && has_lane_kernel((int)HP)) {
-        MultiGeom mg;
-        for (int i = 0; i < kMultiItems; ++i) {
-          mg.it[i].g = g;
-          mg.it[i].out = out;
-          mg.it[i].group_begin = 0;
-        }
-        mg.total_groups = (g.nmaps + 63) / 64;
-        mg.count = 1;
-        return dispatch_lane((int)HP, mg, st);
-      }
-      // the prefetching variant is opt-in: on MI355X it measured equal to the register-load
-      // kernel in steady state (both at the practical HBM rate) and ~2 % slower on the bench
-      if (algo == DCTS_ALGO_PREFETCH) {
-        if (!dma_ok((int)HP, (int)WP, pad, g)) return DCTS_E_UNSUPPORTED;
-        return dispatch_codelet_dma((int)HP, g, out, st);
-      }
-    } else if (algo == DCTS_ALGO_PREFETCH) {
-      return DCTS_E_UNSUPPORTED;
+  switch (c.fam) {
+    case Family::Rect: return dispatch_rect(rect_geom(v), out, store ? 1 : 0, st);
+    case Family::CodeletDma: return dispatch_codelet_dma(HP, g, out, st);
+    case Family::Codelet: return dispatch_codelet(store ? 1 : 0, HP, WP, pad, g, out, st);
+    case Family::Direct: break;
+    case Family::Lane: {
+      MultiGeom mg;
+      for (int i = 0; i < kMultiItems; ++i) mg.it[i] = MultiItem{g, out, 0};
+      mg.total_groups = (g.nmaps + 63) / 64;
+      mg.count = 1;
+      return dispatch_lane(HP, mg, st);
     }
-    return dispatch_codelet(STORE ? 1 : 0, (int)HP, (int)WP, pad, g, out, st);
-  }
-  if constexpr (!STORE) {
-    // every split kernel stages with 16-byte direct-to-LDS loads: a base that is only 4-byte aligned takes the
-    // direct kernel - except where tile2g.hip has the shape: it gathers single dwords and needs neither the alignment
-    // nor (for 71 / 79 / 143 / 159: the cv2 path on odd maps) an unpadded tile
-    const bool aligned16 = (reinterpret_cast<uintptr_t>(x + (long long)c_begin * strideC) & 15) == 0;
-    const bool dense_maps = H == W && strideH == W && g.contiguous && strideC == H * W;
-    const bool split_ok = has_split(HP, WP) && pad == 0 && dense_maps && aligned16;
-    if (algo == DCTS_ALGO_SPLIT && !split_ok) return DCTS_E_UNSUPPORTED;
-    if (algo == DCTS_ALGO_AUTO || algo == DCTS_ALGO_FUSED || algo == DCTS_ALGO_PIPE || algo == DCTS_ALGO_TILE2D) {
-      int fam = (split_ok && aligned16) ? tile_family((int)HP, algo, g.nmaps) : 0;
-      if (!fam && dense_maps && (algo == DCTS_ALGO_AUTO || algo == DCTS_ALGO_TILE2D || algo == DCTS_ALGO_FUSED)) {
-        const bool t2 = algo != DCTS_ALGO_FUSED, fu = algo != DCTS_ALGO_TILE2D;  // an explicit family request is kept
-        if (t2 && pad == 0 && !aligned16 && has_tile2g((int)HP)) fam = 5;
-        if (!fam && fu && pad == 0 && !aligned16 && has_fused2(HP)) fam = 2;  // the two-roles kernel loads dwords into registers
-        if (!fam && fu && pad == 0 && !aligned16 && has_fused(HP)) fam = 1;   // so does the fused kernel
-        if (t2 && pad == 1 && has_tile2g_pad((int)HP)) fam = 6;
-      }
-      if (fam) {
-        TileBatch tb;
-        for (int i = 0; i < kTileItems; ++i) {
-          tb.x[i] = x + (long long)c_begin * strideC;
-          tb.out[i] = out;
-          tb.begin[i] = 0;
-        }
-        tb.begin[1] = tb.begin[kTileItems] = g.nmaps;
-        tb.map_elems = strideC;
-        tb.total = g.nmaps;
-        tb.count = 1;
-        return dispatch_tile_family(fam, (int)HP, tb, st);
-      }
-      if (algo != DCTS_ALGO_AUTO) return DCTS_E_UNSUPPORTED;
-    }
-    if (split_ok && algo != DCTS_ALGO_DIRECT) {
-      const SplitWs sws = split_ws(g.nmaps, (int)HP);
+    case Family::Split: {
+      const SplitWs sws = split_ws(g.nmaps, HP);
       if (!workspace || workspace_bytes < sws.total) return DCTS_E_WORKSPACE;
       if (reinterpret_cast<uintptr_t>(workspace) & 15) return DCTS_E_ALIGN;  // pass 2 stages the intermediate the same way
       basis_forget_range(workspace, sws.total);
-      return dispatch_split((int)HP, g, out, workspace, st);
+      return dispatch_split(HP, g, out, workspace, st);
     }
-  } else {
-    if (algo == DCTS_ALGO_SPLIT || algo == DCTS_ALGO_PIPE) return DCTS_E_UNSUPPORTED;
-    if (algo == DCTS_ALGO_FUSED || algo == DCTS_ALGO_TILE2D) {
-      // coefficients through the large-tile kernels themselves (leaf outputs + k_assemble): what the
-      // parity tests use to check that those kernels compute the DCT and not merely its energy
-      const bool dense = has_split(HP, WP) && pad == 0 && strideH == W && g.contiguous && strideC == H * W &&
-                         (reinterpret_cast<uintptr_t>(x + (long long)c_begin * strideC) & 15) == 0;
-      if (!dense) return DCTS_E_UNSUPPORTED;
+    default: {  // the TileBatch families
+      if (!store) return traits(c.fam).batch(HP, single_batch(v, out), st);
+      // leaf outputs of as many maps as the workspace holds, then k_assemble
       const long long tile_bytes = (long long)HP * WP * 4;
       const long long ws_maps = workspace ? (long long)(workspace_bytes / (size_t)tile_bytes) : 0;
       if (ws_maps < 1 || (reinterpret_cast<uintptr_t>(workspace) & 15)) return DCTS_E_WORKSPACE;
-      const float* x0 = x + (long long)c_begin * strideC;
       float* scratch = reinterpret_cast<float*>(workspace);
       basis_forget_range(workspace, workspace_bytes);
-      if (algo == DCTS_ALGO_TILE2D)
-        return HP == 224 ? dispatch_tile2d_coeff((int)HP, x0, g.nmaps, out, scratch, ws_maps, st)
-                         : dispatch_tile2g_coeff((int)HP, x0, g.nmaps, out, scratch, ws_maps, st);
-      if (has_fused2(HP)) return dispatch_fused2_coeff((int)HP, x0, g.nmaps, out, scratch, ws_maps, st);
-      return dispatch_fused_coeff((int)HP, x0, g.nmaps, out, scratch, ws_maps, st);
+      switch (c.fam) {
+        case Family::Tile2d: return dispatch_tile2d_coeff(HP, v.base(), g.nmaps, out, scratch, ws_maps, st);
+        case Family::Tile2g: return dispatch_tile2g_coeff(HP, v.base(), g.nmaps, out, scratch, ws_maps, st);
+        case Family::Fused2: return dispatch_fused2_coeff(HP, v.base(), g.nmaps, out, scratch, ws_maps, st);
+        default: return dispatch_fused_coeff(HP, v.base(), g.nmaps, out, scratch, ws_maps, st);
+      }
     }
   }
 
-  const DirectWs ws = direct_ws(g.nmaps, (int)HP, (int)WP);
+  const DirectWs ws = direct_ws(g.nmaps, HP, WP);
   if (!workspace) return ws.total ? DCTS_E_WORKSPACE : DCTS_E_NULL;
   if (workspace_bytes < ws.total) return DCTS_E_WORKSPACE;
   char* wsp = reinterpret_cast<char*>(workspace);
   float* CHt = reinterpret_cast<float*>(wsp + ws.off_ch);
   float* CWt = reinterpret_cast<float*>(wsp + ws.off_cw);
   float* T = reinterpret_cast<float*>(wsp + ws.off_t);
-  if (!cache_basis || !basis_cached(workspace, stream, (int)HP, (int)WP)) {
+  if (!cache_basis || !basis_cached(workspace, stream, HP, WP)) {
     basis_forget_range(workspace, ws.total);  // whatever tables lay in the bytes this call uses are gone
-    hipLaunchKernelGGL(k_basis, dim3((unsigned)((HP * HP + 255) / 256)), dim3(256), 0, st, CHt, (int)HP);
-    hipLaunchKernelGGL(k_basis, dim3((unsigned)((WP * WP + 255) / 256)), dim3(256), 0, st, CWt, (int)WP);
+    hipLaunchKernelGGL(k_basis, dim3((unsigned)((HP * HP + 255) / 256)), dim3(256), 0, st, CHt, HP);
+    hipLaunchKernelGGL(k_basis, dim3((unsigned)((WP * WP + 255) / 256)), dim3(256), 0, st, CWt, WP);
     if (cache_basis && hipGetLastError() == hipSuccess)
-      basis_remember(workspace, wsp + ws.off_ch, ws.off_t - ws.off_ch, stream, (int)HP, (int)WP);
+      basis_remember(workspace, wsp + ws.off_ch, ws.off_t - ws.off_ch, stream, HP, WP);
   } else {
     basis_forget_range(wsp + ws.off_t, ws.total - ws.off_t);  // the T tiles may cover another entry's tables
   }
-  hipLaunchKernelGGL((k_energy_direct<STORE>), dim3((unsigned)ws.grid), dim3(kDirectThreads), 0, st,
+  hipLaunchKernelGGL(store ? k_energy_direct<true> : k_energy_direct<false>, dim3((unsigned)ws.grid), dim3(kDirectThreads), 0, st,
                      g, pad, CHt, CWt, T, out);
   return (int)hipGetLastError();
+}
+
+// ---- the coefficient fallback of the weighted and band entry points ------------------------------------------------
+// Which coefficient path their inner calls ask for: the large-tile kernels' own where the tensor suits them, else whatever
+// AUTO picks (codelet / rect / direct). Every inner call covers whole samples or channels of ONE sample, so a sample
+// stride that keeps each sample's base on a 16-byte boundary stands in for adjacency.
+int coeff_algo(const TensorView& v) {
+  const int HP = (int)v.HP();
+  if (v.pad() != 0 || !v.dense_square() || (v.strideN * 4) % 16 != 0 || !v.aligned16()) return DCTS_ALGO_AUTO;
+  if (serves(Family::Tile2d, HP) || serves(Family::Tile2g, HP)) return DCTS_ALGO_TILE2D;
+  if (serves(Family::Fused, HP) || serves(Family::Fused2, HP)) return DCTS_ALGO_FUSED;
+  return DCTS_ALGO_AUTO;
+}
+
+// Sample by sample, runs of at most `chunk` channels (one strided view of x each): coefficients into `coeff` through the
+// coefficient path (scratch: `inner`), then reduce(n, c0, nc) over the nc tiles just written.
+template <class Reduce>
+int coeff_chunks_per_sample(const TensorView& v, long long chunk, int algo, float* coeff, void* inner, size_t inner_bytes,
+                            void* stream, Reduce reduce) {
+  for (int64_t n = 0; n < v.N; ++n) {
+    for (long long c0 = 0; c0 < v.c_count; c0 += chunk) {
+      const long long nc = (v.c_count - c0) < chunk ? (v.c_count - c0) : chunk;
+      TensorView s = v;
+      s.x = v.x + n * v.strideN;
+      s.N = 1;
+      s.c_begin = (int32_t)(v.c_begin + c0);
+      s.c_count = (int32_t)nc;
+      int rc = run(true, s, coeff, inner, inner_bytes, stream, algo, /*cache_basis=*/false);
+      if (rc) return rc;
+      rc = reduce(n, c0, nc);
+      if (rc) return rc;
+    }
+  }
+  return DCTS_OK;
 }
 
 }  // namespace
@@ -593,16 +675,16 @@ int dcts_energy_f32_ex(const float* x, int64_t N, int64_t C_total, int64_t H, in
                        int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
                        float* out_nc, void* workspace, size_t workspace_bytes, void* stream,
                        int32_t algo) {
-  return run<false>(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count,
-                    pad_front_if_odd, out_nc, workspace, workspace_bytes, stream, algo);
+  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  return run(false, v, out_nc, workspace, workspace_bytes, stream, algo);
 }
 
 int dcts_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
                     int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
                     int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd, float* out_nc,
                     void* workspace, size_t workspace_bytes, void* stream) {
-  return run<false>(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count,
-                    pad_front_if_odd, out_nc, workspace, workspace_bytes, stream, DCTS_ALGO_AUTO);
+  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  return run(false, v, out_nc, workspace, workspace_bytes, stream, DCTS_ALGO_AUTO);
 }
 
 int dcts_dct2d_f32_ex(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
@@ -610,16 +692,16 @@ int dcts_dct2d_f32_ex(const float* x, int64_t N, int64_t C_total, int64_t H, int
                       int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
                       float* out_coeff, void* workspace, size_t workspace_bytes, void* stream,
                       int32_t algo) {
-  return run<true>(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count,
-                   pad_front_if_odd, out_coeff, workspace, workspace_bytes, stream, algo);
+  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  return run(true, v, out_coeff, workspace, workspace_bytes, stream, algo);
 }
 
 int dcts_dct2d_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
                    int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
                    int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd, float* out_coeff,
                    void* workspace, size_t workspace_bytes, void* stream) {
-  return run<true>(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count,
-                   pad_front_if_odd, out_coeff, workspace, workspace_bytes, stream, DCTS_ALGO_AUTO);
+  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  return run(true, v, out_coeff, workspace, workspace_bytes, stream, DCTS_ALGO_AUTO);
 }
 
 size_t dcts_weighted_workspace_bytes(int64_t N, int64_t C_count, int64_t H, int64_t W) {
@@ -637,13 +719,10 @@ int dcts_weighted_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t
                              int64_t strideC, int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count,
                              int32_t pad_front_if_odd, const float* weights, float* out_nc, void* workspace,
                              size_t workspace_bytes, void* stream) {
-  if (!x || !out_nc || !weights) return DCTS_E_NULL;
-  if (N <= 0 || C_total <= 0 || H <= 0 || W <= 0) return DCTS_E_SHAPE;
-  if (c_count <= 0 || c_begin < 0 || (int64_t)c_begin + c_count > C_total) return DCTS_E_CHANNELS;
+  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  if (const int rc = validate(v, {out_nc, weights}, Checks::Channels)) return rc;
   if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15)) return workspace ? DCTS_E_ALIGN : DCTS_E_WORKSPACE;
-  const int pad = (pad_front_if_odd && (H % 2 != 0)) ? 1 : 0;
-  const int64_t HP = H + pad, WP = W + pad;
-  const long long tile = (long long)HP * WP * 4;
+  const long long tile = (long long)v.HP() * v.WP() * 4;
   // workspace = [coefficients of a chunk][scratch the coefficient path may use]
   const size_t inner_min = dcts_workspace_bytes(1, 1, H, W);
   if (workspace_bytes < (size_t)(2 * tile) + inner_min) return DCTS_E_WORKSPACE;
@@ -661,28 +740,13 @@ int dcts_weighted_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t
   // inner calls (interior pointer, offset depends on the tile shape) do not cache theirs
   basis_forget(workspace);
   basis_forget_range(workspace, workspace_bytes);
-  // the large-tile kernels where the tensor suits them, else whatever AUTO picks (codelet / direct)
-  // (every inner call covers channels of ONE sample, so the batch stride does not matter)
-  const bool dense = pad == 0 && H == W && strideH == W && strideW == 1 && strideC == H * W && (strideN * 4) % 16 == 0 &&
-                     (reinterpret_cast<uintptr_t>(x + (long long)c_begin * strideC) & 15) == 0;
-  const int algo = (dense && has_tile2d(HP)) ? DCTS_ALGO_TILE2D : (dense && (has_fused(HP) || has_fused2(HP))) ? DCTS_ALGO_FUSED : DCTS_ALGO_AUTO;
-  // maps are taken sample by sample in runs of channels so that a chunk is one strided view of x
-  const long long per_sample = c_count;
-  for (int64_t n = 0; n < N; ++n) {
-    for (long long c0 = 0; c0 < per_sample; c0 += chunk) {
-      const long long nc = (per_sample - c0) < chunk ? (per_sample - c0) : chunk;
-      int rc = run<true>(x + n * strideN, 1, C_total, H, W, strideN, strideC, strideH, strideW, (int32_t)(c_begin + c0), (int32_t)nc,
-                         pad_front_if_odd, coeff, inner, inner_bytes, stream, algo, /*cache_basis=*/false);
-      if (rc) return rc;
-      long long blocks = (nc * 64 + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(k_weighted_energy, dim3((unsigned)blocks), dim3(256), 0, st, coeff, weights, nc, (int)(HP * WP),
-                         out_nc + n * c_count + c0);
-      rc = (int)hipGetLastError();
-      if (rc) return rc;
-    }
-  }
-  return DCTS_OK;
+  const int hw = (int)(v.HP() * v.WP());
+  return coeff_chunks_per_sample(v, chunk, coeff_algo(v), coeff, inner, inner_bytes, stream, [&](int64_t n, long long c0, long long nc) {
+    long long blocks = (nc * 64 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_weighted_energy, dim3((unsigned)blocks), dim3(256), 0, st, coeff, weights, nc, hw, out_nc + n * c_count + c0);
+    return (int)hipGetLastError();
+  });
 }
 
 // ---- K weighted energies per map (band.hip) ------------------------------------------------------------------------
@@ -716,46 +780,26 @@ int dcts_band_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, 
                          int64_t strideC, int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count,
                          int32_t pad_front_if_odd, const float* weights, int32_t K, float* out_nck, void* workspace,
                          size_t workspace_bytes, void* stream, int32_t algo) {
-  if (!x || !out_nck || !weights) return DCTS_E_NULL;
-  if (N <= 0 || C_total <= 0 || H <= 0 || W <= 0) return DCTS_E_SHAPE;
-  if (K < 1 || K > DCTS_BAND_MAX) return DCTS_E_SHAPE;
-  if (c_count <= 0 || c_begin < 0 || (int64_t)c_begin + c_count > C_total) return DCTS_E_CHANNELS;
-  if (strideW != 1 || strideH < W) return DCTS_E_STRIDE;
-  if ((reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(out_nck) & 3) ||
-      (reinterpret_cast<uintptr_t>(weights) & 3))
-    return DCTS_E_ALIGN;
-  const int pad = (pad_front_if_odd && (H % 2 != 0)) ? 1 : 0;
-  const int64_t HP = H + pad, WP = W + pad;
-  if (HP > DCTS_MAX_EDGE || WP > DCTS_MAX_EDGE) return DCTS_E_SHAPE;
-  if (N * (int64_t)c_count >= (1LL << 40)) return DCTS_E_SHAPE;
+  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  if (const int rc = validate(v, {out_nck, weights}, Checks::All, /*shape_ok=*/K >= 1 && K <= DCTS_BAND_MAX)) return rc;
+  const int HP = (int)v.HP(), WP = (int)v.WP();
   if (algo != DCTS_ALGO_AUTO && algo != DCTS_ALGO_CODELET && algo != DCTS_ALGO_DIRECT) return DCTS_E_UNSUPPORTED;
-  const bool fused_ok = has_codelet(HP, WP) && strideH == W;
+  const bool fused_ok = has_codelet(HP, WP) && v.dense_rows();
   if (algo == DCTS_ALGO_CODELET && !fused_ok) return DCTS_E_UNSUPPORTED;
   if (!workspace) return DCTS_E_WORKSPACE;
   if (reinterpret_cast<uintptr_t>(workspace) & 15) return DCTS_E_ALIGN;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
   if (fused_ok && algo != DCTS_ALGO_DIRECT) {
-    const size_t table_bytes = band_table_bytes((int)HP, (int)WP, K);
+    const size_t table_bytes = band_table_bytes(HP, WP, K);
     if (workspace_bytes < table_bytes) return DCTS_E_WORKSPACE;
     basis_forget_range(workspace, table_bytes);  // the table overwrites whatever basis tables lay there
-    MapGeom g;
-    g.x = x;
-    g.nmaps = N * (int64_t)c_count;
-    g.strideN = strideN;
-    g.strideC = strideC;
-    g.strideH = strideH;
-    g.c_count = c_count;
-    g.c_begin = c_begin;
-    g.H = (int)H;
-    g.W = (int)W;
-    g.contiguous = (N == 1 || strideN == (int64_t)c_count * strideC) ? 1 : 0;
-    return dispatch_band((int)HP, pad, g, weights, K, reinterpret_cast<float*>(workspace), out_nck, st);
+    return dispatch_band(HP, v.pad(), map_geom(v), weights, K, reinterpret_cast<float*>(workspace), out_nck, st);
   }
 
   // fallback: coefficients of a chunk of maps through the coefficient path, then one reduction that reads each
   // coefficient once for all K bands
-  long long chunk = band_fallback_chunk(workspace_bytes, (int)HP, (int)WP);
+  long long chunk = band_fallback_chunk(workspace_bytes, HP, WP);
   if (chunk < 1) return DCTS_E_WORKSPACE;
   const long long tile = (long long)HP * WP * 4;
   char* wsp = reinterpret_cast<char*>(workspace);
@@ -767,39 +811,26 @@ int dcts_band_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, 
   // calls (interior pointer) do not cache theirs
   basis_forget(workspace);
   basis_forget_range(workspace, workspace_bytes);
-  // the large-tile kernels' own coefficient path where the tensor suits them, else whatever AUTO picks
-  const bool contiguous = N == 1 || strideN == (int64_t)c_count * strideC;
-  const bool dense = pad == 0 && H == W && strideH == W && strideC == H * W && (strideN * 4) % 16 == 0 &&
-                     (reinterpret_cast<uintptr_t>(x + (long long)c_begin * strideC) & 15) == 0;
-  const int inner_algo = (dense && has_tile2d(HP)) ? DCTS_ALGO_TILE2D
-                         : (dense && (has_fused(HP) || has_fused2(HP))) ? DCTS_ALGO_FUSED : DCTS_ALGO_AUTO;
-  const int hw = (int)(HP * WP);
-  if (chunk >= c_count && (contiguous || inner_algo == DCTS_ALGO_AUTO)) {
+  const int inner_algo = coeff_algo(v);
+  const int hw = HP * WP;
+  if (chunk >= c_count && (v.contiguous() || inner_algo == DCTS_ALGO_AUTO)) {
     // whole samples per chunk: (n, channel) jointly, one strided view of x per call
     const int64_t ns = chunk / c_count;
     for (int64_t n0 = 0; n0 < N; n0 += ns) {
-      const int64_t nn = (N - n0) < ns ? (N - n0) : ns;
-      int rc = run<true>(x + n0 * strideN, nn, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count,
-                         pad_front_if_odd, coeff, inner, inner_bytes, stream, inner_algo, /*cache_basis=*/false);
+      TensorView s = v;
+      s.x = x + n0 * strideN;
+      s.N = (N - n0) < ns ? (N - n0) : ns;
+      int rc = run(true, s, coeff, inner, inner_bytes, stream, inner_algo, /*cache_basis=*/false);
       if (rc) return rc;
-      rc = launch_band_reduce(coeff, weights, nn * c_count, hw, K, out_nck + n0 * c_count * K, st);
+      rc = launch_band_reduce(coeff, weights, s.N * c_count, hw, K, out_nck + n0 * c_count * K, st);
       if (rc) return rc;
     }
     return DCTS_OK;
   }
   if (chunk > c_count) chunk = c_count;
-  for (int64_t n = 0; n < N; ++n) {
-    for (long long c0 = 0; c0 < c_count; c0 += chunk) {
-      const long long nc = (c_count - c0) < chunk ? (c_count - c0) : chunk;
-      int rc = run<true>(x + n * strideN, 1, C_total, H, W, strideN, strideC, strideH, strideW, (int32_t)(c_begin + c0),
-                         (int32_t)nc, pad_front_if_odd, coeff, inner, inner_bytes, stream, inner_algo,
-                         /*cache_basis=*/false);
-      if (rc) return rc;
-      rc = launch_band_reduce(coeff, weights, nc, hw, K, out_nck + (n * c_count + c0) * K, st);
-      if (rc) return rc;
-    }
-  }
-  return DCTS_OK;
+  return coeff_chunks_per_sample(v, chunk, inner_algo, coeff, inner, inner_bytes, stream, [&](int64_t n, long long c0, long long nc) {
+    return launch_band_reduce(coeff, weights, nc, hw, K, out_nck + (n * c_count + c0) * K, st);
+  });
 }
 
 int dcts_batch_sum_f32(const float* energy_nc, int64_t N, int64_t C_count, float* out_c,
@@ -826,43 +857,27 @@ int dcts_energy_multi_f32(const dcts_tensor_item* items, int32_t count, int64_t 
                           int32_t pad_front_if_odd, void* workspace, size_t workspace_bytes, void* stream) {
   if (!items) return DCTS_E_NULL;
   if (count <= 0 || H <= 0 || W <= 0) return DCTS_E_SHAPE;
-  const int pad = (pad_front_if_odd && (H % 2 != 0)) ? 1 : 0;
-  const int64_t HP = H + pad, WP = W + pad;
+  for (int32_t i = 0; i < count; ++i)
+    if (const int rc = validate(view_of(items[i], H, W, pad_front_if_odd), {items[i].out_nc}, Checks::Align)) return rc;
+  const TensorView v0 = view_of(items[0], H, W, pad_front_if_odd);
+  const int HP = (int)v0.HP(), WP = (int)v0.WP(), pad = v0.pad();
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  for (int32_t i = 0; i < count; ++i) {
-    const dcts_tensor_item& t = items[i];
-    if (!t.x || !t.out_nc) return DCTS_E_NULL;
-    if (t.N <= 0 || t.C_total <= 0) return DCTS_E_SHAPE;
-    if (t.c_count <= 0 || t.c_begin < 0 || (int64_t)t.c_begin + t.c_count > t.C_total) return DCTS_E_CHANNELS;
-    if ((reinterpret_cast<uintptr_t>(t.x) & 3) || (reinterpret_cast<uintptr_t>(t.out_nc) & 3)) return DCTS_E_ALIGN;
-  }
   if (has_codelet(HP, WP)) {
-    const int G = codelet_group_size((int)HP);
+    const int G = codelet_group_size(HP);
     for (int32_t i0 = 0; i0 < count; i0 += kMultiItems) {
       const int n = (count - i0) < kMultiItems ? (count - i0) : kMultiItems;
       MultiGeom mg;
       long long groups = 0;
       for (int i = 0; i < n; ++i) {
-        const dcts_tensor_item& t = items[i0 + i];
-        MapGeom& g = mg.it[i].g;
-        g.x = t.x;
-        g.nmaps = t.N * (int64_t)t.c_count;
-        g.strideN = t.strideN;
-        g.strideC = t.strideC;
-        g.strideH = W;
-        g.c_count = t.c_count;
-        g.c_begin = t.c_begin;
-        g.H = (int)H;
-        g.W = (int)W;
-        g.contiguous = (t.N == 1 || t.strideN == (int64_t)t.c_count * t.strideC) ? 1 : 0;
-        mg.it[i].out = t.out_nc;
+        mg.it[i].g = map_geom(view_of(items[i0 + i], H, W, pad_front_if_odd));
+        mg.it[i].out = items[i0 + i].out_nc;
         mg.it[i].group_begin = groups;
-        groups += (g.nmaps + G - 1) / G;
+        groups += (mg.it[i].g.nmaps + G - 1) / G;
       }
       for (int i = n; i < kMultiItems; ++i) mg.it[i] = mg.it[0];
       mg.total_groups = groups;
       mg.count = n;
-      const int rc = dispatch_codelet_multi((int)HP, pad, mg, st);
+      const int rc = dispatch_codelet_multi(HP, pad, mg, st);
       if (rc) return rc;
     }
     return DCTS_OK;
@@ -870,9 +885,8 @@ int dcts_energy_multi_f32(const dcts_tensor_item* items, int32_t count, int64_t 
   // large tiles with a single-launch kernel: the dense tensors go into ONE launch per 32 of them (their
   // maps form one index space: a CU that would get a fraction of a map from one small tensor now
   // draws from all of them); results are those of one call per tensor, bit for bit
-  const int fam = (pad == 0 && H == W && has_split(HP, WP)) ? tile_family((int)HP, DCTS_ALGO_AUTO, 0)
-                  : ((pad == 1 && H == W && has_tile2g_pad((int)HP)) ? 6 : 0);
   TileBatch tb;
+  Family fam = Family::Direct;  // of the open batch
   int nb = 0;
   auto flush = [&]() -> int {
     if (!nb) return DCTS_OK;
@@ -885,28 +899,28 @@ int dcts_energy_multi_f32(const dcts_tensor_item* items, int32_t count, int64_t 
     tb.total = tb.begin[nb];
     tb.count = nb;
     nb = 0;
-    return dispatch_tile_family(fam, (int)HP, tb, st);
+    return traits(fam).batch(HP, tb, st);
   };
   for (int32_t i = 0; i < count; ++i) {
-    const dcts_tensor_item& t = items[i];
-    const float* x0 = t.x + (int64_t)t.c_begin * t.strideC;
-    // (the dword-loading kernels - tile2g, families 5 and 6, and the fused kernels, families 1 and 2 - take any 4-byte-aligned base, the others need 16)
-    const bool dense = fam && t.strideC == H * W && (t.N == 1 || t.strideN == (int64_t)t.c_count * t.strideC) &&
-                       ((reinterpret_cast<uintptr_t>(x0) & 15) == 0 || fam >= 5 || fam == 2 || fam == 1);
-    if (dense) {
+    const TensorView v = view_of(items[i], H, W, pad_front_if_odd);
+    // The family the tensor takes on a 16-byte base: one per call, since shape and density decide it. (Kept as found,
+    // a tensor on a 4-byte base joins the batch where that family tolerates such a base - at 96 and 112 the fused
+    // kernel, where a call of its own takes tile2g.)
+    const Choice c = choose(v, DCTS_ALGO_AUTO, /*store=*/false, /*aligned16=*/true);
+    if (!c.err && traits(c.fam).batch && (v.aligned16() || !traits(c.fam).base16)) {
       if (nb == 0) tb.begin[0] = 0;
-      tb.x[nb] = x0;
-      tb.out[nb] = t.out_nc;
-      tb.begin[nb + 1] = tb.begin[nb] + t.N * (int64_t)t.c_count;
+      fam = c.fam;
+      tb.x[nb] = v.base();
+      tb.out[nb] = items[i].out_nc;
+      tb.begin[nb + 1] = tb.begin[nb] + v.nmaps();
       if (++nb == kTileItems) {
         const int rc = flush();
         if (rc) return rc;
       }
       continue;
     }
-    // everything else: one call per tensor (split / direct), same stream
-    const int rc = run<false>(t.x, t.N, t.C_total, H, W, t.strideN, t.strideC, W, 1, t.c_begin, t.c_count,
-                              pad_front_if_odd, t.out_nc, workspace, workspace_bytes, stream, DCTS_ALGO_AUTO);
+    // everything else: one call per tensor (split / direct / a family of its own), same stream
+    const int rc = run(false, v, items[i].out_nc, workspace, workspace_bytes, stream, DCTS_ALGO_AUTO);
     if (rc) return rc;
   }
   return flush();
@@ -917,13 +931,8 @@ int dcts_energy_mixed_f32(const dcts_shaped_item* items, int32_t count, void* wo
   if (!items) return DCTS_E_NULL;
   if (count <= 0) return DCTS_E_SHAPE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  for (int32_t i = 0; i < count; ++i) {
-    const dcts_tensor_item& t = items[i].t;
-    if (!t.x || !t.out_nc) return DCTS_E_NULL;
-    if (t.N <= 0 || t.C_total <= 0 || items[i].H <= 0 || items[i].W <= 0) return DCTS_E_SHAPE;
-    if (t.c_count <= 0 || t.c_begin < 0 || (int64_t)t.c_begin + t.c_count > t.C_total) return DCTS_E_CHANNELS;
-    if ((reinterpret_cast<uintptr_t>(t.x) & 3) || (reinterpret_cast<uintptr_t>(t.out_nc) & 3)) return DCTS_E_ALIGN;
-  }
+  for (int32_t i = 0; i < count; ++i)
+    if (const int rc = validate(view_of(items[i]), {items[i].t.out_nc}, Checks::Align)) return rc;
   auto eligible = [&](const dcts_shaped_item& it) {
     return it.H == it.W && mixed_has((int)it.H) && !(it.pad_front_if_odd && (it.H % 2 != 0));
   };
@@ -942,22 +951,11 @@ int dcts_energy_mixed_f32(const dcts_shaped_item* items, int32_t count, void* wo
   };
   for (int32_t i = 0; i < count; ++i) {
     if (!eligible(items[i])) continue;
-    const dcts_tensor_item& t = items[i].t;
-    MapGeom& g = mg.it[n].g;
-    g.x = t.x;
-    g.nmaps = t.N * (int64_t)t.c_count;
-    g.strideN = t.strideN;
-    g.strideC = t.strideC;
-    g.strideH = items[i].W;
-    g.c_count = t.c_count;
-    g.c_begin = t.c_begin;
-    g.H = (int)items[i].H;
-    g.W = (int)items[i].W;
-    g.contiguous = (t.N == 1 || t.strideN == (int64_t)t.c_count * t.strideC) ? 1 : 0;
-    mg.it[n].out = t.out_nc;
+    mg.it[n].g = map_geom(view_of(items[i]));
+    mg.it[n].out = items[i].t.out_nc;
     mg.it[n].group_begin = groups;
     const int G = 64 / (int)items[i].H;
-    groups += (g.nmaps + G - 1) / G;
+    groups += (mg.it[n].g.nmaps + G - 1) / G;
     if (++n == kMixedItems) {
       const int rc = flush();
       if (rc) return rc;
