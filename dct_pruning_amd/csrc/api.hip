@@ -8,7 +8,7 @@
 // 2-D DCT-II and the squared coefficients are reduced to one fp32 energy per map.
 //
 // The kernel families are units of their own (codelet.hip, split.hip, fused.hip, fused2.hip, pipe.hip, tile2d.hip,
-// tile2g.hip, rect.hip, rank.hip, band.hip). Here:
+// tile2g.hip, rect.hip, rank.hip, band.hip, half.hip). Here:
 //   k_energy_direct   any (H, W) <= DCTS_MAX_EDGE: separable cosine-matrix transform with
 //                     the basis block staged in LDS; intermediate tile in a caller-provided
 //                     workspace (L2-resident). O(H*W*(H+W)) flops per map: the correct
@@ -641,8 +641,8 @@ const char* dcts_strerror(int code) {
     case DCTS_E_CHANNELS: return "channel slice outside [0, C_total)";
     case DCTS_E_STRIDE: return "rows must be dense: strideW == 1 and strideH >= W";
     case DCTS_E_WORKSPACE: return "workspace missing or smaller than dcts_workspace_bytes()";
-    case DCTS_E_UNSUPPORTED: return "no kernel of the requested family for this shape (rank: edges up to 64)";
-    case DCTS_E_ALIGN: return "pointer not 4-byte aligned (tensors) / 16-byte aligned (workspace)";
+    case DCTS_E_UNSUPPORTED: return "no kernel of the requested family for this shape (rank: edges up to 64), or an unknown dtype";
+    case DCTS_E_ALIGN: return "pointer not aligned: element size (tensors: 4 bytes, fp16 / bf16 input 2), 16 bytes (workspace)";
     default: break;
   }
   if (code > 0) return hipGetErrorString((hipError_t)code);
@@ -831,6 +831,88 @@ int dcts_band_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, 
   return coeff_chunks_per_sample(v, chunk, inner_algo, coeff, inner, inner_bytes, stream, [&](int64_t n, long long c0, long long nc) {
     return launch_band_reduce(coeff, weights, nc, hw, K, out_nck + (n * c_count + c0) * K, st);
   });
+}
+
+// ---- fp16 / bf16 inputs (half.hip) -----------------------------------------------------------------------------------
+// The staged route's workspace: [what the fp32 path needs for the chunk it is given][dense fp32 copy of a chunk of maps].
+// The fp32 part is at the head, so that a direct-kernel call keeps its tables where dcts_energy_f32 would: run() is called as
+// dcts_energy_f32 calls it, so the EXISTING basis-table memo (keyed on the caller's workspace pointer, forgotten through
+// dcts_workspace_invalidate[_range]) serves the staged route as well. That is the only host state it touches; none is added.
+constexpr size_t kHalfStageCap = 64u << 20;  // bytes of upcast maps per chunk at most
+
+static bool is_half_dtype(int32_t dtype) { return dtype == DCTS_DTYPE_F16 || dtype == DCTS_DTYPE_BF16; }
+
+size_t dcts_typed_workspace_bytes(int32_t dtype, int64_t N, int64_t C_count, int64_t H, int64_t W) {
+  if (dtype == DCTS_DTYPE_F32) return dcts_workspace_bytes(N, C_count, H, W);
+  if (!is_half_dtype(dtype) || N <= 0 || C_count <= 0 || H <= 0 || W <= 0) return 0;
+  if (H > DCTS_MAX_EDGE || W > DCTS_MAX_EDGE) return 0;
+  if (has_half(H, W)) return 0;
+  const size_t map = (size_t)H * W * 4;
+  size_t stage = (size_t)(N * C_count) * map;
+  if (stage > kHalfStageCap) stage = kHalfStageCap > map ? kHalfStageCap / map * map : map;
+  return align_up(dcts_workspace_bytes(N, C_count, H, W), 256) + align_up(stage, 256);
+}
+
+int dcts_has_half_kernel(int64_t H, int64_t W) { return has_half(H, W) ? 1 : 0; }
+
+int dcts_energy_typed(const void* x, int32_t dtype, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN,
+                      int64_t strideC, int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count,
+                      int32_t pad_front_if_odd, float* out_nc, void* workspace, size_t workspace_bytes, void* stream) {
+  if (dtype == DCTS_DTYPE_F32)
+    return dcts_energy_f32(reinterpret_cast<const float*>(x), N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin,
+                           c_count, pad_front_if_odd, out_nc, workspace, workspace_bytes, stream);
+  if (!is_half_dtype(dtype)) return DCTS_E_UNSUPPORTED;
+  // the checks of validate(), in its order, with the element size in the alignment test
+  if (!x || !out_nc) return DCTS_E_NULL;
+  if (N <= 0 || C_total <= 0 || H <= 0 || W <= 0) return DCTS_E_SHAPE;
+  if (c_count <= 0 || c_begin < 0 || (int64_t)c_begin + c_count > C_total) return DCTS_E_CHANNELS;
+  if (strideW != 1 || strideH < W) return DCTS_E_STRIDE;
+  if ((reinterpret_cast<uintptr_t>(x) & 1) || (reinterpret_cast<uintptr_t>(out_nc) & 3)) return DCTS_E_ALIGN;
+  const int pad = (pad_front_if_odd && (H % 2 != 0)) ? 1 : 0;
+  if (H + pad > DCTS_MAX_EDGE || W + pad > DCTS_MAX_EDGE) return DCTS_E_SHAPE;
+  if (N * (int64_t)c_count >= (1LL << 40)) return DCTS_E_SHAPE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const uint16_t* xh = reinterpret_cast<const uint16_t*>(x);
+  const bool contiguous = N == 1 || strideN == (int64_t)c_count * strideC;
+
+  if (has_half(H, W) && pad == 0 && strideH == W) {
+    const HalfGeom g{xh, N * (int64_t)c_count, strideN, strideC, c_count, c_begin, contiguous ? 1 : 0};
+    return dispatch_half((int)H, dtype, g, out_nc, st);
+  }
+
+  // staged: upcast a chunk of maps into the workspace, score it through the fp32 path under AUTO. Whole samples per chunk
+  // where the workspace holds one, else runs of channels of one sample (as the band fallback chunks).
+  if (!workspace) return DCTS_E_WORKSPACE;
+  if (reinterpret_cast<uintptr_t>(workspace) & 15) return DCTS_E_ALIGN;
+  const size_t map = (size_t)H * W * 4;
+  // Sized for the whole call and handed to every chunk: direct_ws() and split_ws() never shrink as the map count grows, so
+  // what N * c_count maps need covers any chunk of them (and run() itself refuses a workspace that is too small).
+  const size_t inner_bytes = align_up(dcts_workspace_bytes(N, c_count, H, W), 256);
+  if (workspace_bytes < inner_bytes + map) return DCTS_E_WORKSPACE;
+  long long chunk = (long long)((workspace_bytes - inner_bytes) / map);
+  if ((size_t)chunk * map > kHalfStageCap && kHalfStageCap >= map) chunk = (long long)(kHalfStageCap / map);
+  float* stage = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + inner_bytes);
+  void* inner = inner_bytes ? workspace : nullptr;
+  basis_forget_range(stage, (size_t)chunk * map);  // the upcast maps overwrite whatever tables lay there
+  auto score = [&](int64_t n0, int64_t ns, int32_t c0, int32_t nc) -> int {
+    // samples [n0, n0 + ns), channels [c_begin + c0, c_begin + c0 + nc) of x
+    const HalfGeom g{xh + n0 * strideN, ns * (int64_t)nc, strideN, strideC, nc, c_begin + c0,
+                     (ns == 1 || strideN == (int64_t)nc * strideC) ? 1 : 0};
+    int rc = launch_upcast_half(dtype, g, (int)H, (int)W, strideH, stage, st);
+    if (rc) return rc;
+    const TensorView v{stage, ns, nc, H, W, (int64_t)nc * H * W, H * W, W, 1, 0, nc, pad_front_if_odd != 0};
+    return run(false, v, out_nc + n0 * c_count + c0, inner, inner_bytes, stream, DCTS_ALGO_AUTO);
+  };
+  if (chunk >= c_count) {
+    const int64_t ns = chunk / c_count;
+    for (int64_t n0 = 0; n0 < N; n0 += ns)
+      if (const int rc = score(n0, (N - n0) < ns ? (N - n0) : ns, 0, c_count)) return rc;
+    return DCTS_OK;
+  }
+  for (int64_t n = 0; n < N; ++n)
+    for (int64_t c0 = 0; c0 < c_count; c0 += chunk)
+      if (const int rc = score(n, 1, (int32_t)c0, (int32_t)((c_count - c0) < chunk ? (c_count - c0) : chunk))) return rc;
+  return DCTS_OK;
 }
 
 int dcts_batch_sum_f32(const float* energy_nc, int64_t N, int64_t C_count, float* out_c,

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdint.h>
 
 #include "codelet_sizes.h"
 
@@ -147,6 +148,31 @@ size_t band_table_bytes(int HP, int WP, int K);    // the re-laid weight table T
 int dispatch_band(int HP, int pad, const MapGeom& g, const float* weights, int K, float* table, float* out, hipStream_t st);
 // fallback reduction: out[m][b] = sum_i weights[b][i] * coeff[m][i]^2 over `nmaps` dense tiles of `hw` coefficients
 int launch_band_reduce(const float* coeff, const float* weights, long long nmaps, int hw, int K, float* out, hipStream_t st);
+
+// ---- half.hip: fp16 / bf16 inputs (dcts_energy_typed) -------------------------------------------------------------
+// MapGeom for 2-byte elements (raw bits; the dtype travels beside it). Rows are dense: strideH == W.
+struct HalfGeom {
+  const uint16_t* x;
+  long long nmaps;    // N * c_count
+  long long strideN;  // elements
+  long long strideC;  // elements
+  int c_count;
+  int c_begin;
+  int contiguous;     // 1: map m starts at x + c_begin*strideC + m*strideC
+};
+// dense square edges with a native half kernel: what the six classification nets hook
+#define DCTS_HALF_SIZES(X) X(2) X(4) X(7) X(8) X(14) X(16) X(28) X(32) X(56)
+inline bool has_half(long long H, long long W) {
+  if (H != W) return false;
+#define DCTS_CASE(N) \
+  if (H == N) return true;
+  DCTS_HALF_SIZES(DCTS_CASE)
+#undef DCTS_CASE
+  return false;
+}
+int dispatch_half(int N, int dtype, const HalfGeom& g, float* out, hipStream_t st);
+// the staged route: the g.nmaps maps of g (H x W, row pitch strideH elements) as a dense fp32 array at dst
+int launch_upcast_half(int dtype, const HalfGeom& g, int H, int W, long long strideH, float* dst, hipStream_t st);
 
 // ---- split.hip, split_more.hip: two launches per chunk of maps, intermediate in the workspace ------------------
 struct SplitWs {

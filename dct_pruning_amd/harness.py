@@ -30,8 +30,14 @@ Additions (opt-in, results identical on fixed batches):
                       ops.band_energy_nc: all K bands in one pass over the map): a [C, K] spectrum per hook point in
                       band_score/<net>_limit<L>_<kind><K>/band_*.npy, which bands.collapse turns into imp_*.npy for
                       any band weighting afterwards, on the host (hooks get_feature_hook_bands /
-                      get_feature_hook_densenet_bands / get_feature_hook_u2net_input_bands).
+                      get_feature_hook_densenet_bands / get_feature_hook_u2net_input_bands);
+  autocast="fp16" | "bf16"
+                      the forward sweeps run under torch.autocast; the hooks hand the tensors to ops.energy_nc in
+                      whatever dtype arrives (float16 / bfloat16 maps are scored natively, dcts_energy_typed; a tensor
+                      autocast left in float32 takes the float32 path). Same files; the scores are those of the
+                      autocast forward pass. The "dct" criterion only, and not with deferred=True.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -47,6 +53,7 @@ _rank_nc = ops.rank_nc
 _band_energy_nc = ops.band_energy_nc
 
 CRITERIA = ("dct", "rank", "bands")
+AUTOCAST = {"fp16": torch.float16, "bf16": torch.bfloat16}
 
 # the band criterion's partition (K, kind): imp_score(criterion="bands", bands=...) sets it for its hooks
 _band_cfg = (4, "square")
@@ -324,15 +331,32 @@ class _PointHook:
         return flat if self.width is None else flat.reshape(-1, self.width)
 
 
+def _autocast(autocast, dev):
+    """The context the forward sweeps run in: torch.autocast on the net's device, or nothing."""
+    if autocast is None:
+        return contextlib.nullcontext()
+    return torch.autocast(dev.type, dtype=AUTOCAST[autocast])
+
+
 def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host", group=None, deferred=False,
-              criterion="dct", bands=(4, "square")):
+              criterion="dct", bands=(4, "square"), autocast=None):
     """Counterpart of utils/common.py:367-977. `args` needs .net, .limit (and whatever
     load_data reads when train_loader is None). criterion="rank" scores HRank's feature-map rank instead of the
     DCT energy and writes rank_conv/<net>_limit<L>/rank_*.npy. criterion="bands" with bands=(K, kind) writes the
-    [C, K] band spectrum of every hook point to band_score/<net>_limit<L>_<kind><K>/band_*.npy."""
+    [C, K] band spectrum of every hook point to band_score/<net>_limit<L>_<kind><K>/band_*.npy.
+    autocast="fp16" / "bf16" runs the forward sweeps under torch.autocast and scores the half-precision tensors the
+    hooks then see as they are (criterion "dct" only, not with deferred)."""
     global _acc, _band_cfg
     if criterion not in CRITERIA:
         raise ValueError("imp_score: unknown criterion %r (expected one of %s)" % (criterion, ", ".join(CRITERIA)))
+    if autocast is not None:
+        if autocast not in AUTOCAST:
+            raise ValueError("imp_score: autocast must be None, 'fp16' or 'bf16', got %r" % (autocast,))
+        if deferred:
+            raise ValueError("imp_score: autocast has no deferred mode (no multi-tensor half-precision launch); "
+                             "use single_sweep / accumulate instead")
+        if criterion != "dct":
+            raise ValueError("imp_score: autocast supports criterion='dct' only (the %s kernels take float32)" % criterion)
     if criterion == "rank" and deferred:
         raise ValueError("imp_score: criterion='rank' has no deferred mode; use single_sweep / accumulate instead")
     if criterion == "rank" and args.net == "u2netp":
@@ -373,8 +397,12 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
     _acc = HostAccumulator()
 
     pts = _schedule_for(net, args.net)
-    sweep = u2netp_inference if args.net == "u2netp" else inference
     dev = _net_device(net)
+    sweep_fn = u2netp_inference if args.net == "u2netp" else inference
+
+    def sweep(net, train_loader, limit):
+        with _autocast(autocast, dev):
+            sweep_fn(net, train_loader, limit)
 
     if deferred:
         single_sweep, accumulate = True, "device"

@@ -22,13 +22,18 @@ def _workspace(device, stream_ptr, nbytes):
     return buf
 
 
-def _check_input(x):
+# dcts_energy_typed's DCTS_DTYPE_* of the 2-byte element types energy_nc takes besides float32
+_HALF_DTYPES = {torch.float16: 1, torch.bfloat16: 2}
+
+
+def _check_input(x, half_ok=False):
     if not isinstance(x, torch.Tensor):
         raise TypeError("expected a torch.Tensor")
     if x.dim() != 4:
         raise ValueError("expected [N, C, H, W], got shape %s" % (tuple(x.shape),))
-    if x.dtype != torch.float32:
-        raise TypeError("feature maps must be float32 (the reference path is fp32), got %s" % x.dtype)
+    if x.dtype != torch.float32 and not (half_ok and x.dtype in _HALF_DTYPES):
+        raise TypeError("feature maps must be float32 (the reference path is fp32)%s, got %s"
+                        % (", float16 or bfloat16" if half_ok else "", x.dtype))
     if not x.is_cuda:
         raise RuntimeError(
             "dct_pruning_amd runs on the GPU only: got a %s tensor. There is no CPU fallback; "
@@ -63,20 +68,52 @@ def _call(fn_name, x, c_begin, c_count, pad_front_if_odd, out, algo):
     return out
 
 
+def has_half_kernel(H, W):
+    """True if float16 / bfloat16 maps of a dense (H, W) tile have a kernel of their own (no odd pad); every other
+    shape is upcast chunk by chunk into the workspace and scored by the float32 kernels."""
+    return bool(_lib.load().dcts_has_half_kernel(H, W))
+
+
+def _call_half(x, c_begin, c_count, pad_front_if_odd, out):
+    lib = _lib.load()
+    N, C, H, W = x.shape
+    if x.stride(3) != 1 or x.stride(2) < W:
+        x = x.contiguous()
+    dtype = _HALF_DTYPES[x.dtype]
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    nbytes = lib.dcts_typed_workspace_bytes(dtype, N, c_count, H, W)
+    if lib.dcts_has_half_kernel(H, W) and (x.stride(2) != W or (pad_front_if_odd and H % 2 == 1)):
+        # a native shape the kernel does not take is staged like the others: sized as the header says, for (H, W + 1)
+        nbytes = lib.dcts_typed_workspace_bytes(dtype, N, c_count, H, W + 1)
+    ws = _workspace(x.device, stream, nbytes)
+    with torch.cuda.device(x.device):
+        code = lib.dcts_energy_typed(
+            x.data_ptr(), dtype, N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+            c_begin, c_count, 1 if pad_front_if_odd else 0, out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+    _lib.check(code)
+    return out
+
+
 def energy_nc(x, c_begin=0, c_count=None, pad_front_if_odd=False, algo=ALGO_AUTO, out=None):
     """E[n, j] = sum_{u,v} dct_2d(x[n, c_begin+j], norm='ortho')[u,v]**2  -> [N, c_count] fp32.
 
     pad_front_if_odd=True reproduces torch2dct (utils/common.py:230-239): an odd-H map gets
     one zero row and one zero column in front before the transform.
+    x may be float16 or bfloat16 as well (a forward pass under autocast): every element is upcast exactly and the
+    arithmetic is fp32, so the result is that of x.float() without the copy (dcts_energy_typed; algo must be ALGO_AUTO).
     Enqueues on the current stream of x's device; no synchronisation.
     """
-    _check_input(x)
+    _check_input(x, half_ok=True)
+    if x.dtype != torch.float32 and algo != ALGO_AUTO:
+        raise ValueError("float16 / bfloat16 feature maps take ALGO_AUTO only, got algo=%r" % (algo,))
     c_begin, c_count = _slice(x, c_begin, c_count)
     N = x.shape[0]
     if out is None:
         out = torch.empty((N, c_count), dtype=torch.float32, device=x.device)
     elif out.shape != (N, c_count) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
         raise ValueError("out must be a contiguous float32 [N, c_count] tensor on x's device")
+    if x.dtype != torch.float32:
+        return _call_half(x, c_begin, c_count, pad_front_if_odd, out)
     return _call("dcts_energy_f32_ex", x, c_begin, c_count, pad_front_if_odd, out, algo)
 
 

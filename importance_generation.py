@@ -12,7 +12,9 @@ checkpoint), --input_size, --seed, --single_sweep, --device_accumulate, --deferr
 edges up to 64, so not with --net u2netp, and not with --deferred; bands: the DCT energy of K frequency bands per
 channel, --bands K --band_kind {square,diag}, a [C, K] spectrum per hook point under
 band_score/<net>_limit<L>_<kind><K>/band_*.npy that `python -m dct_pruning_amd.bands` collapses into imp_*.npy for any
-band weighting; not with --deferred). Multi-GPU: launch with
+band weighting; not with --deferred), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
+half-precision feature maps are scored as they are, without an upcast copy; same files, the scores are those of the
+autocast forward pass; --criterion dct only, not with --deferred). Multi-GPU: launch with
 `python -m torch.distributed.run --nproc-per-node G importance_generation.py ...` — hook points
 are sharded over the ranks and rank 0 writes the files.
 """
@@ -50,7 +52,13 @@ def parse_args(argv=None):
     parser.add_argument("--bands", type=int, default=4, help="--criterion bands: number of bands K, 1 ... 8")
     parser.add_argument("--band_kind", type=str, default="square", choices=("square", "diag"),
                         help="--criterion bands: L-infinity shells (square) or anti-diagonal stripes (diag)")
+    parser.add_argument("--autocast", type=str, default=None, choices=("fp16", "bf16"),
+                        help="run the forward sweeps under torch.autocast and score the half-precision feature maps natively")
     args = parser.parse_args(argv)
+    if args.autocast and args.deferred:
+        parser.error("--autocast has no --deferred mode (use --single_sweep / --device_accumulate)")
+    if args.autocast and args.criterion != "dct":
+        parser.error("--autocast supports --criterion dct only")
     if args.criterion == "rank" and args.net == "u2netp":
         parser.error("--criterion rank supports feature maps up to 64 x 64; --net u2netp is out of its scope")
     if args.criterion == "rank" and args.deferred:
@@ -111,7 +119,7 @@ def main(argv=None):
 
     harness.imp_score(net, args, single_sweep=args.single_sweep,
                       accumulate="device" if args.device_accumulate else "host", deferred=args.deferred,
-                      criterion=args.criterion, bands=(args.bands, args.band_kind))
+                      criterion=args.criterion, bands=(args.bands, args.band_kind), autocast=args.autocast)
     if world > 1:
         torch.distributed.destroy_process_group()
 

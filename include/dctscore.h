@@ -45,7 +45,8 @@ extern "C" {
  *    alignment; dcts_workspace_invalidate[_range]), multi / mixed / weighted entry points.
  * 3: dcts_rank_f32 (the HRank criterion) and DCTS_RANK_MAX_EDGE. The band entry points (dcts_band_energy_f32,
  *    dcts_band_workspace_bytes, dcts_has_band_kernel, DCTS_BAND_MAX) were added to 3 WITHOUT a bump: they are purely
- *    additive, and a library that lacks them fails at symbol lookup. */
+ *    additive, and a library that lacks them fails at symbol lookup. The same holds for the fp16 / bf16 entry points
+ *    (dcts_energy_typed, dcts_typed_workspace_bytes, dcts_has_half_kernel, DCTS_DTYPE_*). */
 #define DCTS_ABI_VERSION 3
 
 enum {
@@ -56,7 +57,7 @@ enum {
   DCTS_E_STRIDE = -4,      /* innermost stride != 1 or row stride < W (rows must be dense) */
   DCTS_E_WORKSPACE = -5,   /* workspace smaller than dcts_workspace_bytes() reports     */
   DCTS_E_UNSUPPORTED = -6, /* combination not implemented (see dcts_strerror)           */
-  DCTS_E_ALIGN = -7        /* pointer not 4-byte aligned                                */
+  DCTS_E_ALIGN = -7        /* pointer not aligned to its element size (fp32: 4 bytes)   */
 };
 
 /* Largest tile edge (after the optional odd front pad) any kernel accepts. */
@@ -211,6 +212,39 @@ int dcts_band_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, 
                          int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
                          const float* weights, int32_t K, float* out_nck, void* workspace, size_t workspace_bytes,
                          void* stream, int32_t algo);
+
+/*
+ * dcts_energy_f32 for feature maps of another element type: what a forward pass under autocast hands to a hook.
+ *
+ *   dtype      DCTS_DTYPE_F32 forwards to dcts_energy_f32 (x is then a const float*); DCTS_DTYPE_F16 (IEEE binary16) and
+ *              DCTS_DTYPE_BF16 (bfloat16) are scored as described below; anything else returns DCTS_E_UNSUPPORTED.
+ *   x, strides, c_begin, c_count, pad_front_if_odd, out_nc    as for dcts_energy_f32. Strides are in ELEMENTS of `dtype`;
+ *              x must be aligned to the element size (DCTS_E_ALIGN otherwise). out_nc is always fp32.
+ * Every element is converted to fp32 exactly (both conversions are exact, fp16 subnormals included) and all arithmetic is
+ * fp32: the result is that of dcts_energy_f32 on the upcast tensor up to the kernels' rounding.
+ *   - Dense square maps (strideH == W, no odd pad taken) of the edges dcts_has_half_kernel names - 2, 4, 7, 8, 14, 16, 28,
+ *     32, 56: every hook point of the six classification nets - have a kernel of their own (half.hip) that reads the 2-byte
+ *     elements straight from memory: the codelet kernel's schedule with another load. No workspace (NULL is fine).
+ *   - Every other shape up to DCTS_MAX_EDGE is staged: a chunk of maps of the scored slice is upcast into the workspace
+ *     (dense, 16-byte aligned) and scored by dcts_energy_f32's own kernels; whole samples per chunk where the workspace
+ *     holds one, runs of channels of one sample otherwise. Bit for bit what dcts_energy_f32 gives for a dense 16-byte
+ *     aligned fp32 copy of the slice.
+ *   workspace  >= dcts_typed_workspace_bytes(dtype, N, c_count, H, W) bytes, 16-byte aligned; that is 0 where the native
+ *              kernel takes the shape. A call of such a shape that the native kernel does not take (rows with a pitch,
+ *              7 x 7 with the odd pad) is staged too: size its workspace as for (H, W + 1), which is never native and
+ *              never needs less. The staged route chunks by what it is given (at most 64 MiB of upcast maps per chunk);
+ *              DCTS_E_WORKSPACE if that is less than the fp32 path's own need plus one upcast map.
+ * A map's value depends on that map alone (not on N, the channel slice, the other maps or the launch count): no atomics,
+ * +0.0 for an all-zero map, a NaN map touches only its own output. Only enqueues on `stream`; no new host state.
+ */
+enum { DCTS_DTYPE_F32 = 0, DCTS_DTYPE_F16 = 1, DCTS_DTYPE_BF16 = 2 };
+int dcts_energy_typed(const void* x, int32_t dtype, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                      int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
+                      int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
+                      float* out_nc, void* workspace, size_t workspace_bytes, void* stream);
+size_t dcts_typed_workspace_bytes(int32_t dtype, int64_t N, int64_t C_count, int64_t H, int64_t W);
+/* 1 if the native fp16 / bf16 kernel takes a dense (H, W) map (no odd pad). */
+int dcts_has_half_kernel(int64_t H, int64_t W);
 
 /*
  * Fused batch reduction for benchmarking and for the single-sweep harness:
