@@ -2,9 +2,10 @@
 //   out[m][b] = sum_{u,v} weights[b][u][v] * c[u][v]^2,  c = dct_2d(map m, norm='ortho'),  b = 0 ... K-1.
 // With one-hot weights (dct_pruning_amd/bands.py) that is the energy of K frequency bands of every map.
 //
-//   k_band_codelet   the codelet kernel's schedule (codelet.hip, codelet_group): pass 1 lane = column, transpose through
-//                    the wave's LDS slab, pass 2 lane = row u with the WP coefficients of that row in registers. The
-//                    reduction differs: KB accumulators e[b] = fma(wt[b][u][l], w[l] * w[l], e[b]) instead of one, then
+//   k_band_codelet   the codelet kernel's schedule with the slab geometry, grid rule, fence and segmented reduction of
+//                    codelet_schedule.hpp: pass 1 lane = column, transpose through the wave's LDS slab (plain stores),
+//                    pass 2 lane = row u with the N coefficients of that row in registers. What this unit adds is the
+//                    epilogue: KB accumulators e[b] = fma(wt[b][u][l], w[l] * w[l], e[b]) instead of one, then
 //                    the segmented wave reduction once per band and K stores per map. KB = K rounded up to 1, 2, 4, 8;
 //                    the bands above K have zero weights and are not stored. A band's chain of FMAs and its reduction
 //                    tree depend on nothing but the map's row and the band's weights: the result of a map is the same
@@ -24,6 +25,7 @@
 #include <type_traits>
 
 #include "../../include/dctscore.h"
+#include "codelet_schedule.hpp"
 #include "codelet_sizes.h"
 #include "dct_codelets.hpp"
 #include "dcts_internal.h"
@@ -31,17 +33,6 @@
 using namespace dctsi;
 
 namespace {
-
-// the transpose slab of codelet.hip's CodeletCfg, square tiles only (same paddings: they were searched for there)
-template <int N>
-struct BandCfg {
-  static constexpr int G = 64 / N;  // maps per wave per iteration
-  static constexpr int S = N == 7 ? 8 : (N == 10 || N == 14) ? 17 : N == 20 ? 25 : N == 28 ? 33 : (N | 1);
-  static constexpr int MAP_LDS = N == 7 ? 71 : N * S;
-  static constexpr int WAVE_LDS = G * MAP_LDS;
-  static constexpr int WAVES = (WAVE_LDS * 4 * 4 <= 49152) ? 4 : ((WAVE_LDS * 4 * 2 <= 49152) ? 2 : 1);
-  static constexpr int GRID_WAVES_PER_CU = (N * N >= 48 * 48) ? 256 : ((N * N >= 8 * 8) ? 512 : 32);
-};
 
 template <int KB>
 struct WVec {
@@ -82,9 +73,9 @@ __global__ __launch_bounds__(256) void k_band_table(const float* __restrict__ we
 }
 
 template <int N, int PAD, int KB>
-__global__ __launch_bounds__((64 * BandCfg<N>::WAVES)) void k_band_codelet(MapGeom g, const float* __restrict__ T, int K,
+__global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_band_codelet(MapGeom g, const float* __restrict__ T, int K,
                                                                            float* __restrict__ out) {
-  using Cfg = BandCfg<N>;
+  using Cfg = CodeletCfg<N>;
   constexpr int G = Cfg::G, S = Cfg::S, MAP_LDS = Cfg::MAP_LDS, WAVES = Cfg::WAVES;
   constexpr int W = N - PAD;  // data row length == row stride (dense rows)
   __shared__ float slab[WAVES][Cfg::WAVE_LDS];
@@ -135,10 +126,7 @@ __global__ __launch_bounds__((64 * BandCfg<N>::WAVES)) void k_band_codelet(MapGe
         dst[kk * S] = y[kk];
       });
     }
-    // the wave's own LDS traffic is in order; only the compiler must not reorder
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_fence();
 
     // ---- pass 2: row DCT-II, lane = row u ------------------------------------------------------
     float z[N], w[N];
@@ -191,13 +179,7 @@ __global__ __launch_bounds__((64 * BandCfg<N>::WAVES)) void k_band_codelet(MapGe
     dcts::static_for<KB>([&](auto ib) DCTS_LAMBDA_INLINE {
       constexpr int b = decltype(ib)::value;
       float eb = act ? e[b] : 0.f;
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) {
-        if (off < N) {
-          const float t = __shfl_down(eb, off, 64);
-          if (c + off < N) eb += t;
-        }
-      }
+      DCTS_MAP_SUM(N, eb, c)
       e[b] = eb;
     });
     if (has && c == 0) {
@@ -208,9 +190,7 @@ __global__ __launch_bounds__((64 * BandCfg<N>::WAVES)) void k_band_codelet(MapGe
         if (b < K) o[b] = e[b] * sc;
       });
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_fence();
   }
 }
 
@@ -245,13 +225,9 @@ __global__ __launch_bounds__(256) void k_band_reduce(const float* __restrict__ c
 
 template <int N, int PAD, int KB>
 int launch_band(const MapGeom& g, const float* T, int K, float* out, hipStream_t st) {
-  using Cfg = BandCfg<N>;
+  using Cfg = CodeletCfg<N>;
   const long long ngroups = (g.nmaps + Cfg::G - 1) / Cfg::G;
-  long long blocks = (ngroups + Cfg::WAVES - 1) / Cfg::WAVES;
-  const long long cap = (long long)num_cus() * Cfg::GRID_WAVES_PER_CU / Cfg::WAVES;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((k_band_codelet<N, PAD, KB>), dim3((unsigned)blocks), dim3(64 * Cfg::WAVES), 0, st, g, T, K, out);
+  hipLaunchKernelGGL((k_band_codelet<N, PAD, KB>), dim3(codelet_grid<N>(ngroups)), dim3(64 * Cfg::WAVES), 0, st, g, T, K, out);
   return (int)hipGetLastError();
 }
 
@@ -284,21 +260,9 @@ int dispatch_band(int HP, int pad, const MapGeom& g, const float* weights, int K
   hipLaunchKernelGGL(k_band_table, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, weights, table, HP, HP, K, KB);
   int rc = (int)hipGetLastError();
   if (rc) return rc;
-#define DCTS_CASE(N)                                                \
-  case N:                                                           \
-    if (pad) {                                                      \
-      if constexpr ((N % 2) == 0 && N >= 2)                         \
-        return launch_band_k<N, 1>(KB, g, table, K, out, st);       \
-      else                                                          \
-        return DCTS_E_UNSUPPORTED;                                  \
-    }                                                               \
-    return launch_band_k<N, 0>(KB, g, table, K, out, st);
-  switch (HP) {
-    DCTS_CODELET_SIZES(DCTS_CASE)
-    default:
-      return DCTS_E_UNSUPPORTED;
-  }
-#undef DCTS_CASE
+  return switch_codelet_size(HP, pad, [&](auto n, auto p) {
+    return launch_band_k<decltype(n)::value, decltype(p)::value>(KB, g, table, K, out, st);
+  });
 }
 
 int launch_band_reduce(const float* coeff, const float* weights, long long nmaps, int hw, int K, float* out,

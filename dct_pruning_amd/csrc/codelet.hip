@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "../../include/dctscore.h"
+#include "codelet_schedule.hpp"
 #include "codelet_sizes.h"
 #include "dct_codelets.hpp"
 #include "dcts_internal.h"
@@ -33,31 +34,6 @@ namespace {
 // ---------------------------------------------------------------------------------------
 // codelet family
 // ---------------------------------------------------------------------------------------
-template <int HP, int WP>
-struct CodeletCfg {
-  static constexpr int EDGE = HP > WP ? HP : WP;
-  static constexpr int G = 64 / EDGE;           // maps per wave per iteration
-  // LDS row stride S and per-map stride: odd S is conflict-free inside one map; when several maps
-  // share a wave the pair (S, MAP_LDS) below keeps the G*edge lanes of a half-wave on distinct
-  // banks for both the column-wise store and the row-wise load (brute-force search over paddings,
-  // SQ_LDS_BANK_CONFLICT was 18-47 % of LDS cycles before for these edges)
-  static constexpr int S = (HP == WP && WP == 7) ? 8 : (HP == WP && (WP == 10 || WP == 14)) ? 17
-                         : (HP == WP && WP == 20) ? 25 : (HP == WP && WP == 28) ? 33 : (WP | 1);
-  static constexpr int MAP_LDS = (HP == WP && WP == 7) ? 71 : HP * S;  // floats per map in the transpose slab
-  static constexpr int WAVE_LDS = G * MAP_LDS;  // floats per wave
-  // waves per workgroup: keep a workgroup's slab <= 48 KiB so >= 3 workgroups fit a CU
-  static constexpr int WAVES = (WAVE_LDS * 4 * 4 <= 49152) ? 4 : ((WAVE_LDS * 4 * 2 <= 49152) ? 2 : 1);
-  // Waves launched per CU at most (the grid-stride loop takes the rest). NOT one residency (12 waves per CU
-  // at 56 x 56): a grid several times the residency, whose workgroups the dispatcher hands out as CUs free up,
-  // is faster than persistent waves in lock step - sweep of this cap on the bench's own launches, waves per
-  // CU -> % of the HBM peak: 56 x 56 (344 k maps) 32: 67.2, 128...512: 69.6, 2048: 66.3; 28 x 28 (819 k) 32:
-  // 68.4, 256: 74.7, 512: 76.4, 2048: 72.5; 14 x 14 (2.4 M) 32: 69.4, 512: 74.7, 2048: 74.9; 200 MB launches
-  // of 8 / 14 / 28 / 32: 62 -> 71, 62 -> 71, 66 -> 72.5, 68 -> 73.5; whole ResNet-50 step 3259 -> 3561 Mmaps/s.
-  // (4 x 4 and 2 x 2 groups are 1 KB and 512 B: there the wider grid costs more in wave launches than it
-  // gains - 70 -> 61 % and 50 -> 46 % - and the cap stays at 32.)
-  static constexpr int GRID_WAVES_PER_CU = (HP * WP >= 48 * 48) ? 256 : ((HP * WP >= 8 * 8) ? 512 : 32);
-};
-
 // ds_write_addtid_b32 in the codelet kernel's transposing stores where a wave holds one map (edges 36 ... 64): same box,
 // 200 MB launches, % of the HBM peak: 56: 60.7 -> 61.5-62.3, 48: 60.8 -> 63.0, 36: 52.9 -> 54.0, 64: 52.9 -> 54.2; the
 // 4.3 GB in-step launch is unchanged within noise (the kernel is VALU-bound there). Bit-identical results.
@@ -74,11 +50,13 @@ __device__ __forceinline__ void lds_write_addtid4(unsigned base, float a, float 
       : "memory", "m0");
 }
 
-// one group of G maps: both passes, the LDS transpose and the reduction (see the header comment)
+// one group of G maps: both passes, the LDS transpose and the reduction (see the header comment). Every caller passes
+// HP == WP (the dispatchers refuse anything else; rect.hip serves non-square tiles), so the pass-2 role (g2, k, act2) equals
+// the pass-1 role. The two-role form stays: folding it changes the instruction order of 90 of this unit's 149 kernels.
 template <int HP, int WP, int PAD, bool STORE_COEFF>
 __device__ __forceinline__ void codelet_group(const MapGeom& g, float* __restrict__ out, long long grp,
                                               float* my, int g1, int c, int g2, int k, bool act1, bool act2) {
-  using Cfg = CodeletCfg<HP, WP>;
+  using Cfg = CodeletCfg<HP>;
   constexpr int G = Cfg::G, S = Cfg::S, MAP_LDS = Cfg::MAP_LDS;
   constexpr int W = WP - PAD;  // data row length == row stride (dense rows)
   // ---- pass 1: column DCT-II of length HP, lane = column -------------------------
@@ -130,10 +108,7 @@ __device__ __forceinline__ void codelet_group(const MapGeom& g, float* __restric
       dst[kk * S] = y[kk];
     });
   }
-  // the wave's own LDS traffic is in order; only the compiler must not reorder
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_fence();
 
   // ---- pass 2: row DCT-II of length WP, lane = row --------------------------------
   float z[WP], w[WP];
@@ -164,28 +139,19 @@ __device__ __forceinline__ void codelet_group(const MapGeom& g, float* __restric
       e = fmaf(w[l], w[l], e);
     });
     if (!act2) e = 0.f;
-    // segmented reduction over the HP lanes of each map (lane k == 0 ends with the sum)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      if (off < HP) {
-        const float t = __shfl_down(e, off, 64);
-        if (k + off < HP) e += t;
-      }
-    }
+    DCTS_MAP_SUM(HP, e, k)
     if (act2 && k == 0 && m2 < g.nmaps) {
       constexpr float sc = float(4.0 / (double(HP) * double(WP)));
       out[m2] = e * sc;
     }
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_fence();
 }
 
 template <int HP, int WP, int PAD, bool STORE_COEFF>
-__global__ __launch_bounds__((64 * CodeletCfg<HP, WP>::WAVES)) void k_energy_codelet(
+__global__ __launch_bounds__((64 * CodeletCfg<HP>::WAVES)) void k_energy_codelet(
     MapGeom g, float* __restrict__ out) {
-  using Cfg = CodeletCfg<HP, WP>;
+  using Cfg = CodeletCfg<HP>;
   constexpr int G = Cfg::G, WAVES = Cfg::WAVES;
   __shared__ float slab[WAVES][Cfg::WAVE_LDS];
 
@@ -208,8 +174,8 @@ __global__ __launch_bounds__((64 * CodeletCfg<HP, WP>::WAVES)) void k_energy_cod
 
 // Several hooked tensors of the same tile shape in ONE launch (MultiGeom, dcts_internal.h)
 template <int HP, int WP, int PAD>
-__global__ __launch_bounds__((64 * CodeletCfg<HP, WP>::WAVES)) void k_energy_codelet_multi(MultiGeom mg) {
-  using Cfg = CodeletCfg<HP, WP>;
+__global__ __launch_bounds__((64 * CodeletCfg<HP>::WAVES)) void k_energy_codelet_multi(MultiGeom mg) {
+  using Cfg = CodeletCfg<HP>;
   constexpr int G = Cfg::G, WAVES = Cfg::WAVES;
   __shared__ float slab[WAVES][Cfg::WAVE_LDS];
 
@@ -240,7 +206,7 @@ __global__ __launch_bounds__((64 * CodeletCfg<HP, WP>::WAVES)) void k_energy_cod
 constexpr int mixed_slab_floats() {
   int m = 0;
 #define DCTS_CASE(N) \
-  if (CodeletCfg<N, N>::WAVE_LDS > m) m = CodeletCfg<N, N>::WAVE_LDS;
+  if (CodeletCfg<N>::WAVE_LDS > m) m = CodeletCfg<N>::WAVE_LDS;
   DCTS_MIXED_SIZES(DCTS_CASE)
 #undef DCTS_CASE
   return m;
@@ -249,7 +215,7 @@ constexpr int kMixedWaves = 4;
 
 template <int E>
 __device__ __forceinline__ void mixed_group(const MultiItem& item, long long grp, float* my, int lane) {
-  using Cfg = CodeletCfg<E, E>;
+  using Cfg = CodeletCfg<E>;
   const int g1 = lane / E, c = lane - g1 * E;  // square tile: pass-1 and pass-2 roles coincide
   const bool act = g1 < Cfg::G;
   codelet_group<E, E, 0, false>(item.g, item.out, grp, my, g1, c, g1, c, act, act);
@@ -428,9 +394,9 @@ __global__ __launch_bounds__((64 * LaneCfg<N>::WAVES)) void k_energy_lane_multi(
 // 28 % of the wave's cycles in k_energy_codelet). Pass 1 then reads its column from the linear
 // LDS image (lane = column: consecutive addresses, conflict-free).
 template <int N>
-__global__ __launch_bounds__((64 * CodeletCfg<N, N>::WAVES)) void k_energy_codelet_dma(
+__global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_energy_codelet_dma(
     MapGeom g, float* __restrict__ out) {
-  using Cfg = CodeletCfg<N, N>;
+  using Cfg = CodeletCfg<N>;
   constexpr int G = Cfg::G, S = Cfg::S, MAP_LDS = Cfg::MAP_LDS, WAVES = Cfg::WAVES;
   constexpr int NN = N * N;
   constexpr int QPG = G * NN / 4;                // 16-byte quads per full group
@@ -490,9 +456,7 @@ __global__ __launch_bounds__((64 * CodeletCfg<N, N>::WAVES)) void k_energy_codel
         dst[kk * S] = y[kk];
       });
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_fence();
     // ---- pass 2: row DCT-II, lane = row -----------------------------------------------
     float z[N], w[N];
     {
@@ -515,13 +479,7 @@ __global__ __launch_bounds__((64 * CodeletCfg<N, N>::WAVES)) void k_energy_codel
       e = fmaf(w[l], w[l], e);
     });
     if (!act) e = 0.f;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      if (off < N) {
-        const float t = __shfl_down(e, off, 64);
-        if (c + off < N) e += t;
-      }
-    }
+    DCTS_MAP_SUM(N, e, c)
     if (valid && c == 0) {
       constexpr float sc = float(4.0 / (double(N) * double(N)));
       out[m1] = e * sc;
@@ -531,88 +489,39 @@ __global__ __launch_bounds__((64 * CodeletCfg<N, N>::WAVES)) void k_energy_codel
 
 template <int HP, int WP, int PAD, bool STORE>
 int launch_codelet(const MapGeom& g, float* out, hipStream_t st) {
-  using Cfg = CodeletCfg<HP, WP>;
+  using Cfg = CodeletCfg<HP>;
   const long long ngroups = (g.nmaps + Cfg::G - 1) / Cfg::G;
-  long long blocks = (ngroups + Cfg::WAVES - 1) / Cfg::WAVES;
-  const long long cap = (long long)num_cus() * Cfg::GRID_WAVES_PER_CU / Cfg::WAVES;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((k_energy_codelet<HP, WP, PAD, STORE>), dim3((unsigned)blocks),
-                     dim3(64 * Cfg::WAVES), 0, st, g, out);
+  hipLaunchKernelGGL((k_energy_codelet<HP, WP, PAD, STORE>), dim3(codelet_grid<HP>(ngroups)), dim3(64 * Cfg::WAVES), 0, st, g, out);
   return (int)hipGetLastError();
 }
 
 template <int N>
 int launch_codelet_dma(const MapGeom& g, float* out, hipStream_t st) {
-  using Cfg = CodeletCfg<N, N>;
+  using Cfg = CodeletCfg<N>;
   if constexpr ((Cfg::G * N * N) % 4 != 0) {
     return DCTS_E_UNSUPPORTED;
   } else {
     const long long ngroups = (g.nmaps + Cfg::G - 1) / Cfg::G;
-    long long blocks = (ngroups + Cfg::WAVES - 1) / Cfg::WAVES;
     // persistent grid = exactly one residency: every wave then loops over many groups and the
     // prefetch of group i+1 overlaps the arithmetic of group i
-    static const int per_cu = [] {
-      int n = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_energy_codelet_dma<N>, 64 * Cfg::WAVES, 0) != hipSuccess ||
-          n < 1)
-        n = 1;
-      return n;
-    }();
-    const long long cap = (long long)num_cus() * per_cu;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL((k_energy_codelet_dma<N>), dim3((unsigned)blocks), dim3(64 * Cfg::WAVES), 0, st, g, out);
+    const long long cap = (long long)num_cus() * blocks_per_cu<k_energy_codelet_dma<N>, Cfg::WAVES>();
+    hipLaunchKernelGGL((k_energy_codelet_dma<N>), dim3(grid_blocks(ngroups, Cfg::WAVES, cap)), dim3(64 * Cfg::WAVES), 0, st, g, out);
     return (int)hipGetLastError();
   }
 }
 
-template <bool STORE>
-int dispatch_codelet_impl(int HP, int WP, int pad, const MapGeom& g, float* out, hipStream_t st) {
-  if (HP != WP) return DCTS_E_UNSUPPORTED;
-#define DCTS_CASE(N)                                                          \
-  case N:                                                                     \
-    if (pad) {                                                                \
-      if constexpr ((N % 2) == 0 && N >= 2)                                   \
-        return launch_codelet<N, N, 1, STORE>(g, out, st);                    \
-      else                                                                    \
-        return DCTS_E_UNSUPPORTED;                                            \
-    }                                                                         \
-    return launch_codelet<N, N, 0, STORE>(g, out, st);
-  switch (HP) {
-    DCTS_CODELET_SIZES(DCTS_CASE)
-    default:
-      return DCTS_E_UNSUPPORTED;
-  }
-#undef DCTS_CASE
-}
-
 template <int HP, int WP, int PAD>
 int launch_codelet_multi(const MultiGeom& mg, hipStream_t st) {
-  using Cfg = CodeletCfg<HP, WP>;
-  long long blocks = (mg.total_groups + Cfg::WAVES - 1) / Cfg::WAVES;
-  const long long cap = (long long)num_cus() * Cfg::GRID_WAVES_PER_CU / Cfg::WAVES;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((k_energy_codelet_multi<HP, WP, PAD>), dim3((unsigned)blocks), dim3(64 * Cfg::WAVES), 0, st,
-                     mg);
+  hipLaunchKernelGGL((k_energy_codelet_multi<HP, WP, PAD>), dim3(codelet_grid<HP>(mg.total_groups)), dim3(64 * CodeletCfg<HP>::WAVES),
+                     0, st, mg);
   return (int)hipGetLastError();
 }
 
 template <int N>
 int launch_lane(const MultiGeom& mg, hipStream_t st) {
   using Cfg = LaneCfg<N>;
-  static const int per_cu = [] {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_energy_lane_multi<N>, 64 * Cfg::WAVES, 0) != hipSuccess || n < 1)
-      n = 1;
-    return n;
-  }();
-  long long blocks = (mg.total_groups + Cfg::WAVES - 1) / Cfg::WAVES;
-  const long long cap = (long long)num_cus() * per_cu;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((k_energy_lane_multi<N>), dim3((unsigned)blocks), dim3(64 * Cfg::WAVES), 0, st, mg);
+  const long long cap = (long long)num_cus() * blocks_per_cu<k_energy_lane_multi<N>, Cfg::WAVES>();
+  hipLaunchKernelGGL((k_energy_lane_multi<N>), dim3(grid_blocks(mg.total_groups, Cfg::WAVES, cap)), dim3(64 * Cfg::WAVES), 0, st, mg);
   return (int)hipGetLastError();
 }
 
@@ -623,7 +532,7 @@ namespace dctsi {
 int codelet_group_size(int HP) {
   if (has_lane_kernel(HP)) return 64;
 #define DCTS_CASE(N) \
-  if (HP == N) return CodeletCfg<N, N>::G;
+  if (HP == N) return CodeletCfg<N>::G;
   DCTS_CODELET_SIZES(DCTS_CASE)
 #undef DCTS_CASE
   return 0;
@@ -642,21 +551,16 @@ int dispatch_codelet_dma(int N, const MapGeom& g, float* out, hipStream_t st) {
 }
 
 int dispatch_codelet(int store, int HP, int WP, int pad, const MapGeom& g, float* out, hipStream_t st) {
-  return store ? dispatch_codelet_impl<true>(HP, WP, pad, g, out, st) : dispatch_codelet_impl<false>(HP, WP, pad, g, out, st);
+  if (HP != WP) return DCTS_E_UNSUPPORTED;  // rect.hip serves non-square tiles
+  return switch_codelet_size(HP, pad, [&](auto n, auto p) {
+    constexpr int N = decltype(n)::value, PAD = decltype(p)::value;
+    return store ? launch_codelet<N, N, PAD, true>(g, out, st) : launch_codelet<N, N, PAD, false>(g, out, st);
+  });
 }
 
 int dispatch_codelet_mixed(const MixedGeom& mg, hipStream_t st) {
-  static const int per_cu = [] {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_energy_codelet_mixed, 64 * kMixedWaves, 0) != hipSuccess || n < 1)
-      n = 1;
-    return n;
-  }();
-  long long blocks = (mg.total_groups + kMixedWaves - 1) / kMixedWaves;
-  const long long cap = (long long)num_cus() * per_cu;  // one residency of persistent waves
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_energy_codelet_mixed, dim3((unsigned)blocks), dim3(64 * kMixedWaves), 0, st, mg);
+  const long long cap = (long long)num_cus() * blocks_per_cu<k_energy_codelet_mixed, kMixedWaves>();  // one residency of persistent waves
+  hipLaunchKernelGGL(k_energy_codelet_mixed, dim3(grid_blocks(mg.total_groups, kMixedWaves, cap)), dim3(64 * kMixedWaves), 0, st, mg);
   return (int)hipGetLastError();
 }
 
@@ -673,21 +577,9 @@ int dispatch_lane(int n, const MultiGeom& mg, hipStream_t st) {
 
 int dispatch_codelet_multi(int HP, int pad, const MultiGeom& mg, hipStream_t st) {
   if (has_lane_kernel(HP) && pad == 0) return dispatch_lane(HP, mg, st);
-#define DCTS_CASE(N)                                        \
-  case N:                                                   \
-    if (pad) {                                              \
-      if constexpr ((N % 2) == 0 && N >= 2)                 \
-        return launch_codelet_multi<N, N, 1>(mg, st);       \
-      else                                                  \
-        return DCTS_E_UNSUPPORTED;                          \
-    }                                                       \
-    return launch_codelet_multi<N, N, 0>(mg, st);
-  switch (HP) {
-    DCTS_CODELET_SIZES(DCTS_CASE)
-    default:
-      return DCTS_E_UNSUPPORTED;
-  }
-#undef DCTS_CASE
+  return switch_codelet_size(HP, pad, [&](auto n, auto p) {
+    return launch_codelet_multi<decltype(n)::value, decltype(n)::value, decltype(p)::value>(mg, st);
+  });
 }
 
 }  // namespace dctsi

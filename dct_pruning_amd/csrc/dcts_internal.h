@@ -22,7 +22,9 @@ struct MapGeom {
   int contiguous;     // 1: map m starts at x + c_begin*strideC + m*strideC (no div needed)
 };
 
-__device__ __forceinline__ const float* map_base(const MapGeom& g, long long m) {
+// first element of map m of the scored channel slice; Geom is MapGeom or HalfGeom (below)
+template <class Geom>
+__device__ __forceinline__ auto map_base(const Geom& g, long long m) -> decltype(g.x) {
   if (g.contiguous) return g.x + (long long)g.c_begin * g.strideC + m * g.strideC;
   const long long n = m / g.c_count;
   const long long j = m - n * g.c_count;

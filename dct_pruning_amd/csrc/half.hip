@@ -1,12 +1,11 @@
 // half.hip - per-map DCT energy of IEEE fp16 and bfloat16 feature maps (dcts_energy_typed, include/dctscore.h).
 //
-//   k_energy_half    the codelet kernel's schedule (codelet.hip, codelet_group) restated for 2-byte elements, as band.hip
-//                    restates it for K accumulators: pass 1 lane = column, transpose through the wave's LDS slab (same
-//                    paddings), pass 2 lane = row u, one chain of FMAs over the row's squares, the segmented wave reduction,
-//                    the 4 / N^2 scale, the same grid rule. Only the load is new: an element becomes fp32 EXACTLY (fp16 ->
-//                    fp32 and bf16 -> fp32 are both exact, fp16 subnormals included: they are fp32 normals) and every
-//                    instruction after that is fp32 in codelet_group's order. A map's value depends on that map alone: not
-//                    on N, the channel slice, its position in the wave or the launch count.
+//   k_energy_half    the fp32 codelet kernel's schedule with the slab geometry, grid rule, fence and segmented reduction of
+//                    codelet_schedule.hpp (plain transposing stores, the fp32 kernel's energy epilogue). What this unit adds
+//                    is the load: an element becomes fp32 EXACTLY (fp16 -> fp32 and bf16 -> fp32 are both exact, fp16
+//                    subnormals included: they are fp32 normals) and every instruction after that is fp32 in the fp32
+//                    kernel's order. A map's value depends on that map alone: not on N, the channel slice, its position
+//                    in the wave or the launch count.
 //                    The load is one 2-byte load per lane and row: the fp32 kernel's instruction count for half the
 //                    bytes, any 2-byte-aligned base. (Packed pairs - one dword = two adjacent columns, split in registers
 //                    after a DPP exchange - were built and measured: 3-19 % slower at 56, 28, 32, 16, 8 and 4, within
@@ -17,30 +16,13 @@
 #include <stdint.h>
 
 #include "../../include/dctscore.h"
+#include "codelet_schedule.hpp"
 #include "dct_codelets.hpp"
 #include "dcts_internal.h"
 
 using namespace dctsi;
 
 namespace {
-
-// the transpose slab of codelet.hip's CodeletCfg, square tiles only (same paddings: they were searched for there)
-template <int N>
-struct HalfCfg {
-  static constexpr int G = 64 / N;  // maps per wave per iteration
-  static constexpr int S = N == 7 ? 8 : (N == 10 || N == 14) ? 17 : N == 20 ? 25 : N == 28 ? 33 : (N | 1);
-  static constexpr int MAP_LDS = N == 7 ? 71 : N * S;
-  static constexpr int WAVE_LDS = G * MAP_LDS;
-  static constexpr int WAVES = (WAVE_LDS * 4 * 4 <= 49152) ? 4 : ((WAVE_LDS * 4 * 2 <= 49152) ? 2 : 1);
-  static constexpr int GRID_WAVES_PER_CU = (N * N >= 48 * 48) ? 256 : ((N * N >= 8 * 8) ? 512 : 32);
-};
-
-__device__ __forceinline__ const uint16_t* half_map_base(const HalfGeom& g, long long m) {
-  if (g.contiguous) return g.x + (long long)g.c_begin * g.strideC + m * g.strideC;
-  const long long n = m / g.c_count;
-  const long long j = m - n * g.c_count;
-  return g.x + n * g.strideN + (g.c_begin + j) * g.strideC;
-}
 
 // the low 16 bits of `bits` as an fp16 (DT == DCTS_DTYPE_F16) or bfloat16 element, exactly, in fp32
 template <int DT>
@@ -54,8 +36,8 @@ __device__ __forceinline__ float half_to_float(unsigned bits) {
 }
 
 template <int N, int DT>
-__global__ __launch_bounds__((64 * HalfCfg<N>::WAVES)) void k_energy_half(HalfGeom g, float* __restrict__ out) {
-  using Cfg = HalfCfg<N>;
+__global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_energy_half(HalfGeom g, float* __restrict__ out) {
+  using Cfg = CodeletCfg<N>;
   constexpr int G = Cfg::G, S = Cfg::S, MAP_LDS = Cfg::MAP_LDS, WAVES = Cfg::WAVES;
   __shared__ float slab[WAVES][Cfg::WAVE_LDS];
 
@@ -74,7 +56,7 @@ __global__ __launch_bounds__((64 * HalfCfg<N>::WAVES)) void k_energy_half(HalfGe
     const long long m1 = grp * G + g1;
     const bool has = act && m1 < g.nmaps;
     // lanes without a map load some valid map instead; their results are never stored
-    const uint16_t* p = half_map_base(g, has ? m1 : g.nmaps - 1) + (has ? c : 0);
+    const uint16_t* p = map_base(g, has ? m1 : g.nmaps - 1) + (has ? c : 0);
     float xr[N];
     dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
       constexpr int r = decltype(i)::value;
@@ -90,10 +72,7 @@ __global__ __launch_bounds__((64 * HalfCfg<N>::WAVES)) void k_energy_half(HalfGe
         dst[kk * S] = y[kk];
       });
     }
-    // the wave's own LDS traffic is in order; only the compiler must not reorder
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_fence();
 
     // ---- pass 2: row DCT-II, lane = row u ------------------------------------------------------
     float z[N], w[N];
@@ -113,20 +92,12 @@ __global__ __launch_bounds__((64 * HalfCfg<N>::WAVES)) void k_energy_half(HalfGe
     });
     if (!act) e = 0.f;
     // segmented reduction over the N lanes of each map (lane c == 0 ends with the sum)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      if (off < N) {
-        const float t = __shfl_down(e, off, 64);
-        if (c + off < N) e += t;
-      }
-    }
+    DCTS_MAP_SUM(N, e, c)
     if (has && c == 0) {
       constexpr float sc = float(4.0 / (double(N) * double(N)));
       out[m1] = e * sc;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_fence();
   }
 }
 
@@ -140,19 +111,15 @@ __global__ __launch_bounds__(256) void k_upcast_half(HalfGeom g, int H, int W, l
     const long long m = i / hw;
     const int e = (int)(i - m * hw);
     const int h = e / W, w = e - h * W;
-    dst[i] = half_to_float<DT>(half_map_base(g, m)[h * strideH + w]);
+    dst[i] = half_to_float<DT>(map_base(g, m)[h * strideH + w]);
   }
 }
 
 template <int N, int DT>
 int launch_half(const HalfGeom& g, float* out, hipStream_t st) {
-  using Cfg = HalfCfg<N>;
+  using Cfg = CodeletCfg<N>;
   const long long ngroups = (g.nmaps + Cfg::G - 1) / Cfg::G;
-  long long blocks = (ngroups + Cfg::WAVES - 1) / Cfg::WAVES;
-  const long long cap = (long long)num_cus() * Cfg::GRID_WAVES_PER_CU / Cfg::WAVES;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((k_energy_half<N, DT>), dim3((unsigned)blocks), dim3(64 * Cfg::WAVES), 0, st, g, out);
+  hipLaunchKernelGGL((k_energy_half<N, DT>), dim3(codelet_grid<N>(ngroups)), dim3(64 * Cfg::WAVES), 0, st, g, out);
   return (int)hipGetLastError();
 }
 
@@ -177,14 +144,11 @@ int dispatch_half(int N, int dtype, const HalfGeom& g, float* out, hipStream_t s
 int launch_upcast_half(int dtype, const HalfGeom& g, int H, int W, long long strideH, float* dst, hipStream_t st) {
   if (dtype != DCTS_DTYPE_F16 && dtype != DCTS_DTYPE_BF16) return DCTS_E_UNSUPPORTED;
   const long long total = g.nmaps * (long long)H * W;
-  long long blocks = (total + 255) / 256;
-  const long long cap = (long long)num_cus() * 32;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
+  const unsigned blocks = grid_blocks(total, 256, (long long)num_cus() * 32);  // one thread per element and step
   if (dtype == DCTS_DTYPE_F16)
-    hipLaunchKernelGGL(k_upcast_half<DCTS_DTYPE_F16>, dim3((unsigned)blocks), dim3(256), 0, st, g, H, W, strideH, dst);
+    hipLaunchKernelGGL(k_upcast_half<DCTS_DTYPE_F16>, dim3(blocks), dim3(256), 0, st, g, H, W, strideH, dst);
   else
-    hipLaunchKernelGGL(k_upcast_half<DCTS_DTYPE_BF16>, dim3((unsigned)blocks), dim3(256), 0, st, g, H, W, strideH, dst);
+    hipLaunchKernelGGL(k_upcast_half<DCTS_DTYPE_BF16>, dim3(blocks), dim3(256), 0, st, g, H, W, strideH, dst);
   return (int)hipGetLastError();
 }
 
