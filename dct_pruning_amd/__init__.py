@@ -28,8 +28,9 @@ from .ops import (  # noqa: F401
     has_band_kernel,
     has_codelet,
     has_half_kernel,
+    has_nhwc_kernel,
     rank_nc,
     weighted_energy_nc,
 )
 
-__all__ = ["energy_nc", "energy_multi", "energy_mixed", "dct2d", "batch_sum", "has_codelet", "weighted_energy_nc", "rank_nc", "band_energy_nc", "has_band_kernel", "has_half_kernel", "ALGO_AUTO", "ALGO_DIRECT", "ALGO_CODELET", "ALGO_SPLIT", "ALGO_PREFETCH", "ALGO_FUSED", "ALGO_PIPE", "ALGO_LANE", "ALGO_TILE2D", "ALGO_RECT"]
+__all__ = ["energy_nc", "energy_multi", "energy_mixed", "dct2d", "batch_sum", "has_codelet", "weighted_energy_nc", "rank_nc", "band_energy_nc", "has_band_kernel", "has_half_kernel", "has_nhwc_kernel", "ALGO_AUTO", "ALGO_DIRECT", "ALGO_CODELET", "ALGO_SPLIT", "ALGO_PREFETCH", "ALGO_FUSED", "ALGO_PIPE", "ALGO_LANE", "ALGO_TILE2D", "ALGO_RECT"]

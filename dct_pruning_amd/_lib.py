@@ -49,6 +49,9 @@ SIGNATURES = {
                                          _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "dcts_typed_workspace_bytes": (_sz, [_i32, _i64, _i64, _i64, _i64]),
     "dcts_has_half_kernel": (ctypes.c_int, [_i64, _i64]),
+    "dcts_has_nhwc_kernel": (ctypes.c_int, [_i64, _i64]),
+    "dcts_nhwc_workspace_bytes": (_sz, [_i32, _i64, _i64, _i64, _i64]),
+    "dcts_energy_nhwc": (ctypes.c_int, [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
     "dcts_debug_stream_read_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
 }
 

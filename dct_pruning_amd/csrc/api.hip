@@ -915,6 +915,32 @@ int dcts_energy_typed(const void* x, int32_t dtype, int64_t N, int64_t C_total, 
   return DCTS_OK;
 }
 
+// ---- channels-last maps (nhwc.hip) ------------------------------------------------------------------------------------
+int dcts_has_nhwc_kernel(int64_t H, int64_t W) { return has_nhwc(H, W) ? 1 : 0; }
+
+// nothing is staged: the native kernels read the tensor where it lies, and every other shape is refused
+size_t dcts_nhwc_workspace_bytes(int32_t, int64_t, int64_t, int64_t, int64_t) { return 0; }
+
+int dcts_energy_nhwc(const void* x, int32_t dtype, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN,
+                     int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count, float* out_nc, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  (void)workspace;
+  (void)workspace_bytes;
+  if (dtype != DCTS_DTYPE_F32 && !is_half_dtype(dtype)) return DCTS_E_UNSUPPORTED;
+  // the checks of dcts_energy_typed, in its order; the stride rules are those of the channels-last layout
+  if (!x || !out_nc) return DCTS_E_NULL;
+  if (N <= 0 || C_total <= 0 || H <= 0 || W <= 0) return DCTS_E_SHAPE;
+  if (c_count <= 0 || c_begin < 0 || (int64_t)c_begin + c_count > C_total) return DCTS_E_CHANNELS;
+  if (strideW < C_total || strideH / W < strideW) return DCTS_E_STRIDE;  // strideH >= W * strideW without the product
+  const uintptr_t elem_mask = dtype == DCTS_DTYPE_F32 ? 3 : 1;
+  if ((reinterpret_cast<uintptr_t>(x) & elem_mask) || (reinterpret_cast<uintptr_t>(out_nc) & 3)) return DCTS_E_ALIGN;
+  if (H > DCTS_MAX_EDGE || W > DCTS_MAX_EDGE) return DCTS_E_SHAPE;
+  if (N * (int64_t)c_count >= (1LL << 40)) return DCTS_E_SHAPE;
+  if (!has_nhwc(H, W)) return DCTS_E_UNSUPPORTED;  // the caller's copy into the NCHW layout stays the caller's
+  const NhwcGeom g{x, N, strideN, strideH, strideW, c_begin, c_count};
+  return dispatch_nhwc((int)H, dtype, g, out_nc, reinterpret_cast<hipStream_t>(stream));
+}
+
 int dcts_batch_sum_f32(const float* energy_nc, int64_t N, int64_t C_count, float* out_c,
                        void* stream) {
   if (!energy_nc || !out_c) return DCTS_E_NULL;

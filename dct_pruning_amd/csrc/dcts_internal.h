@@ -176,6 +176,30 @@ int dispatch_half(int N, int dtype, const HalfGeom& g, float* out, hipStream_t s
 // the staged route: the g.nmaps maps of g (H x W, row pitch strideH elements) as a dense fp32 array at dst
 int launch_upcast_half(int dtype, const HalfGeom& g, int H, int W, long long strideH, float* dst, hipStream_t st);
 
+// ---- nhwc.hip: channels-last maps of fp32 / fp16 / bf16 elements (dcts_energy_nhwc) ---------------------------------
+// element (n, c, h, w) of the scored slice is x[n*strideN + h*strideH + w*strideW + c_begin + c] (elements of the dtype that
+// travels beside the descriptor): the channel stride is 1
+struct NhwcGeom {
+  const void* x;
+  long long N;
+  long long strideN, strideH, strideW;  // elements
+  int c_begin;
+  int c_count;
+};
+// dense square edges with a native channels-last kernel (no odd pad)
+#define DCTS_NHWC_LANE_SIZES(X) X(2) X(4) X(7) X(8)        /* lane = channel, the map in registers */
+#define DCTS_NHWC_BLOCK_SIZES(X) X(14) X(16) X(28) X(32)   /* a channel block of whole maps through LDS */
+inline bool has_nhwc(long long H, long long W) {
+  if (H != W) return false;
+#define DCTS_CASE(N) \
+  if (H == N) return true;
+  DCTS_NHWC_LANE_SIZES(DCTS_CASE)
+  DCTS_NHWC_BLOCK_SIZES(DCTS_CASE)
+#undef DCTS_CASE
+  return H == 56;  // strips of rows through LDS
+}
+int dispatch_nhwc(int N, int dtype, const NhwcGeom& g, float* out, hipStream_t st);
+
 // ---- split.hip, split_more.hip: two launches per chunk of maps, intermediate in the workspace ------------------
 struct SplitWs {
   long long chunk_maps;

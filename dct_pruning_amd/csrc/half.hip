@@ -19,21 +19,11 @@
 #include "codelet_schedule.hpp"
 #include "dct_codelets.hpp"
 #include "dcts_internal.h"
+#include "half_convert.hpp"
 
 using namespace dctsi;
 
 namespace {
-
-// the low 16 bits of `bits` as an fp16 (DT == DCTS_DTYPE_F16) or bfloat16 element, exactly, in fp32
-template <int DT>
-__device__ __forceinline__ float half_to_float(unsigned bits) {
-  if constexpr (DT == DCTS_DTYPE_F16) {
-    const unsigned short h = (unsigned short)bits;
-    return (float)__builtin_bit_cast(_Float16, h);
-  } else {
-    return __builtin_bit_cast(float, bits << 16);
-  }
-}
 
 template <int N, int DT>
 __global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_energy_half(HalfGeom g, float* __restrict__ out) {

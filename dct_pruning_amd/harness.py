@@ -36,6 +36,9 @@ Additions (opt-in, results identical on fixed batches):
                       whatever dtype arrives (float16 / bfloat16 maps are scored natively, dcts_energy_typed; a tensor
                       autocast left in float32 takes the float32 path). Same files; the scores are those of the
                       autocast forward pass. The "dct" criterion only, and not with deferred=True.
+  channels_last=True  the net and every input batch are converted to torch.channels_last; the hooks hand on whatever
+                      layout arrives and ops.energy_nc reads channels-last tensors where they lie (dcts_energy_nhwc).
+                      Same files. Combines with autocast. The "dct" criterion only, not with deferred=True, not u2netp.
 """
 import contextlib
 import os
@@ -338,14 +341,27 @@ def _autocast(autocast, dev):
     return torch.autocast(dev.type, dtype=AUTOCAST[autocast])
 
 
+class _ChannelsLastLoader:
+    """The (data, target) batches of `loader` with data in torch.channels_last."""
+
+    def __init__(self, loader):
+        self.loader = loader
+
+    def __iter__(self):
+        for data, target in self.loader:
+            yield data.contiguous(memory_format=torch.channels_last), target
+
+
 def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host", group=None, deferred=False,
-              criterion="dct", bands=(4, "square"), autocast=None):
+              criterion="dct", bands=(4, "square"), autocast=None, channels_last=False):
     """Counterpart of utils/common.py:367-977. `args` needs .net, .limit (and whatever
     load_data reads when train_loader is None). criterion="rank" scores HRank's feature-map rank instead of the
     DCT energy and writes rank_conv/<net>_limit<L>/rank_*.npy. criterion="bands" with bands=(K, kind) writes the
     [C, K] band spectrum of every hook point to band_score/<net>_limit<L>_<kind><K>/band_*.npy.
     autocast="fp16" / "bf16" runs the forward sweeps under torch.autocast and scores the half-precision tensors the
-    hooks then see as they are (criterion "dct" only, not with deferred)."""
+    hooks then see as they are (criterion "dct" only, not with deferred).
+    channels_last=True converts the net (in place) and every input batch to torch.channels_last; the tensors the hooks
+    then see are scored in the layout they arrive in (criterion "dct" only, not with deferred, not u2netp)."""
     global _acc, _band_cfg
     if criterion not in CRITERIA:
         raise ValueError("imp_score: unknown criterion %r (expected one of %s)" % (criterion, ", ".join(CRITERIA)))
@@ -357,6 +373,16 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
                              "use single_sweep / accumulate instead")
         if criterion != "dct":
             raise ValueError("imp_score: autocast supports criterion='dct' only (the %s kernels take float32)" % criterion)
+    if channels_last:
+        if deferred:
+            raise ValueError("imp_score: channels_last has no deferred mode (the multi-tensor launches take NCHW tensors); "
+                             "use single_sweep / accumulate instead")
+        if criterion != "dct":
+            raise ValueError("imp_score: channels_last supports criterion='dct' only (the %s kernels take NCHW tensors)"
+                             % criterion)
+        if args.net == "u2netp":
+            raise ValueError("imp_score: channels_last does not cover u2netp (dict batches, and no channels-last "
+                             "kernel for its 288 x 288 maps)")
     if criterion == "rank" and deferred:
         raise ValueError("imp_score: criterion='rank' has no deferred mode; use single_sweep / accumulate instead")
     if criterion == "rank" and args.net == "u2netp":
@@ -391,6 +417,10 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
     if train_loader is None:
         from .data import load_data
         train_loader, _ = load_data(args)
+
+    if channels_last:
+        net.to(memory_format=torch.channels_last)
+        train_loader = _ChannelsLastLoader(train_loader)
 
     print("==> Generating importance score..")
     print("Importance Score is located at ./" + out_dir)

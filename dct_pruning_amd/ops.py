@@ -94,6 +94,48 @@ def _call_half(x, c_begin, c_count, pad_front_if_odd, out):
     return out
 
 
+def has_nhwc_kernel(H, W):
+    """True if channels-last maps of a dense (H, W) tile have a kernel of their own (dcts_energy_nhwc; no odd pad);
+    every other shape that is not W-contiguous is copied into the NCHW layout first."""
+    return bool(_lib.load().dcts_has_nhwc_kernel(H, W))
+
+
+ROUTE_NCHW, ROUTE_NHWC, ROUTE_COPY = 1, 2, 3
+
+
+def energy_route(shape, stride, pad_front_if_odd=False, algo=ALGO_AUTO, has_kernel=None):
+    """How energy_nc reaches a kernel for a tensor of this shape and these strides (elements), decided in this order:
+    ROUTE_NCHW  rows are W-contiguous (stride(3) == 1, stride(2) >= W): the NCHW kernels read it as it is;
+    ROUTE_NHWC  the channel stride is 1, stride(3) >= C, stride(2) >= W * stride(3), (H, W) has a channels-last kernel,
+                no odd pad is taken and algo is ALGO_AUTO: dcts_energy_nhwc reads it as it is;
+    ROUTE_COPY  everything else: .contiguous() first, then ROUTE_NCHW.
+    `has_kernel(H, W)` defaults to has_nhwc_kernel (the built library); tests pass their own to stay off the GPU."""
+    N, C, H, W = shape
+    sN, sC, sH, sW = stride
+    if sW == 1 and sH >= W:
+        return ROUTE_NCHW
+    pad = bool(pad_front_if_odd) and H % 2 == 1
+    if sC == 1 and sW >= C and sH >= W * sW and not pad and algo == ALGO_AUTO:
+        if (has_nhwc_kernel if has_kernel is None else has_kernel)(H, W):
+            return ROUTE_NHWC
+    return ROUTE_COPY
+
+
+_NHWC_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def _call_nhwc(x, c_begin, c_count, out):
+    lib = _lib.load()
+    N, C, H, W = x.shape
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    with torch.cuda.device(x.device):
+        code = lib.dcts_energy_nhwc(
+            x.data_ptr(), _NHWC_DTYPES[x.dtype], N, C, H, W, x.stride(0), x.stride(2), x.stride(3),
+            c_begin, c_count, out.data_ptr(), None, 0, stream)
+    _lib.check(code)
+    return out
+
+
 def energy_nc(x, c_begin=0, c_count=None, pad_front_if_odd=False, algo=ALGO_AUTO, out=None):
     """E[n, j] = sum_{u,v} dct_2d(x[n, c_begin+j], norm='ortho')[u,v]**2  -> [N, c_count] fp32.
 
@@ -101,6 +143,9 @@ def energy_nc(x, c_begin=0, c_count=None, pad_front_if_odd=False, algo=ALGO_AUTO
     one zero row and one zero column in front before the transform.
     x may be float16 or bfloat16 as well (a forward pass under autocast): every element is upcast exactly and the
     arithmetic is fp32, so the result is that of x.float() without the copy (dcts_energy_typed; algo must be ALGO_AUTO).
+    A channels-last tensor (torch.channels_last, or a channel slice / sample-strided view of one) of a shape
+    has_nhwc_kernel names is read where it lies (energy_route: dcts_energy_nhwc, any of the three dtypes); every other
+    tensor whose rows are not W-contiguous is copied with .contiguous() first.
     Enqueues on the current stream of x's device; no synchronisation.
     """
     _check_input(x, half_ok=True)
@@ -112,6 +157,8 @@ def energy_nc(x, c_begin=0, c_count=None, pad_front_if_odd=False, algo=ALGO_AUTO
         out = torch.empty((N, c_count), dtype=torch.float32, device=x.device)
     elif out.shape != (N, c_count) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
         raise ValueError("out must be a contiguous float32 [N, c_count] tensor on x's device")
+    if energy_route(x.shape, x.stride(), pad_front_if_odd, algo) == ROUTE_NHWC:
+        return _call_nhwc(x, c_begin, c_count, out)
     if x.dtype != torch.float32:
         return _call_half(x, c_begin, c_count, pad_front_if_odd, out)
     return _call("dcts_energy_f32_ex", x, c_begin, c_count, pad_front_if_odd, out, algo)

@@ -14,7 +14,10 @@ channel, --bands K --band_kind {square,diag}, a [C, K] spectrum per hook point u
 band_score/<net>_limit<L>_<kind><K>/band_*.npy that `python -m dct_pruning_amd.bands` collapses into imp_*.npy for any
 band weighting; not with --deferred), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
 half-precision feature maps are scored as they are, without an upcast copy; same files, the scores are those of the
-autocast forward pass; --criterion dct only, not with --deferred). Multi-GPU: launch with
+autocast forward pass; --criterion dct only, not with --deferred), --channels_last (the net and its inputs run in
+torch.channels_last and the feature maps are scored in the layout they arrive in, without a transposing copy where a
+channels-last kernel exists; same files; combines with --autocast; --criterion dct only, not with --deferred or
+--net u2netp). Multi-GPU: launch with
 `python -m torch.distributed.run --nproc-per-node G importance_generation.py ...` — hook points
 are sharded over the ranks and rank 0 writes the files.
 """
@@ -54,7 +57,15 @@ def parse_args(argv=None):
                         help="--criterion bands: L-infinity shells (square) or anti-diagonal stripes (diag)")
     parser.add_argument("--autocast", type=str, default=None, choices=("fp16", "bf16"),
                         help="run the forward sweeps under torch.autocast and score the half-precision feature maps natively")
+    parser.add_argument("--channels_last", action="store_true",
+                        help="run the net and its inputs in torch.channels_last and score the feature maps in that layout")
     args = parser.parse_args(argv)
+    if args.channels_last and args.deferred:
+        parser.error("--channels_last has no --deferred mode (use --single_sweep / --device_accumulate)")
+    if args.channels_last and args.criterion != "dct":
+        parser.error("--channels_last supports --criterion dct only")
+    if args.channels_last and args.net == "u2netp":
+        parser.error("--channels_last does not cover --net u2netp")
     if args.autocast and args.deferred:
         parser.error("--autocast has no --deferred mode (use --single_sweep / --device_accumulate)")
     if args.autocast and args.criterion != "dct":
@@ -119,7 +130,8 @@ def main(argv=None):
 
     harness.imp_score(net, args, single_sweep=args.single_sweep,
                       accumulate="device" if args.device_accumulate else "host", deferred=args.deferred,
-                      criterion=args.criterion, bands=(args.bands, args.band_kind), autocast=args.autocast)
+                      criterion=args.criterion, bands=(args.bands, args.band_kind), autocast=args.autocast,
+                      channels_last=args.channels_last)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -46,7 +46,8 @@ extern "C" {
  * 3: dcts_rank_f32 (the HRank criterion) and DCTS_RANK_MAX_EDGE. The band entry points (dcts_band_energy_f32,
  *    dcts_band_workspace_bytes, dcts_has_band_kernel, DCTS_BAND_MAX) were added to 3 WITHOUT a bump: they are purely
  *    additive, and a library that lacks them fails at symbol lookup. The same holds for the fp16 / bf16 entry points
- *    (dcts_energy_typed, dcts_typed_workspace_bytes, dcts_has_half_kernel, DCTS_DTYPE_*). */
+ *    (dcts_energy_typed, dcts_typed_workspace_bytes, dcts_has_half_kernel, DCTS_DTYPE_*) and for the channels-last ones
+ *    (dcts_energy_nhwc, dcts_nhwc_workspace_bytes, dcts_has_nhwc_kernel). */
 #define DCTS_ABI_VERSION 3
 
 enum {
@@ -245,6 +246,35 @@ int dcts_energy_typed(const void* x, int32_t dtype, int64_t N, int64_t C_total, 
 size_t dcts_typed_workspace_bytes(int32_t dtype, int64_t N, int64_t C_count, int64_t H, int64_t W);
 /* 1 if the native fp16 / bf16 kernel takes a dense (H, W) map (no odd pad). */
 int dcts_has_half_kernel(int64_t H, int64_t W);
+
+/*
+ * Per-map DCT energy of CHANNELS-LAST feature maps (torch.channels_last; what NHWC convolutions hand to a hook), read
+ * where they lie instead of through a transposing copy (nhwc.hip).
+ *
+ *   x          logical shape [N, C_total, H, W] of `dtype` elements (DCTS_DTYPE_F32, _F16 or _BF16; anything else returns
+ *              DCTS_E_UNSUPPORTED); element (n, c, h, w) is at x[n*strideN + h*strideH + w*strideW + c]: the channel
+ *              stride is 1. strideW >= C_total and strideH >= W*strideW (DCTS_E_STRIDE otherwise). strideW may exceed the
+ *              channel count and x may sit at any element offset, so a channel-sliced view of a channels-last tensor is
+ *              fine. Strides are in ELEMENTS of `dtype`; x is aligned to the element size (DCTS_E_ALIGN otherwise).
+ *   c_begin, c_count    channel slice to score, inside [0, C_total).
+ *   out_nc     [N, c_count] fp32 as for dcts_energy_f32. There is no odd front pad.
+ *   workspace  unused: dcts_nhwc_workspace_bytes() is 0 for every shape the entry point takes. NULL is fine.
+ * Shapes: dense square maps of the edges dcts_has_nhwc_kernel names - 2, 4, 7, 8 (one lane holds one map: the 64 lanes
+ * of a wave are 64 consecutive channels) and 14, 16, 28, 32 (a block of 32 / 32 / 16 / 8 channels of one sample goes
+ * through LDS, then the codelet kernels' schedule) and 56 (4 channels, strips of 8 rows through LDS, one wave per
+ * map). Every other shape returns DCTS_E_UNSUPPORTED: the
+ * copy into the NCHW layout stays with the caller.
+ * Every element is converted to fp32 exactly and all arithmetic is fp32. A map's value depends on that map alone (not on
+ * N, C_total, the channel slice, its position in a wave or block, or the launch count): no atomics, +0.0 for an
+ * all-zero map, a NaN map touches only its own output. The value is that of dcts_energy_f32 / dcts_energy_typed on the
+ * NCHW copy up to the kernels' rounding (same codelets; the summation order differs at 2, 4, 7, 8).
+ * Only enqueues on `stream`; no host state.
+ */
+int dcts_has_nhwc_kernel(int64_t H, int64_t W);
+size_t dcts_nhwc_workspace_bytes(int32_t dtype, int64_t N, int64_t C_count, int64_t H, int64_t W);
+int dcts_energy_nhwc(const void* x, int32_t dtype, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                     int64_t strideN, int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count,
+                     float* out_nc, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Fused batch reduction for benchmarking and for the single-sweep harness:
