@@ -21,6 +21,7 @@
 
 #include "../../include/dctscore.h"
 #include "dcts_internal.h"
+#include "grid_caps.h"
 #include "rect.h"
 #ifdef DCTS_FUSED_STAMPS
 #include "split_common.hpp"  // g_fused_stamps
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(kSumCh * kSumSl) void k_running_mean_multi(UpdateBa
 
 // Score variant in the coefficient domain: out[m] = sum_{u,v} weights[u,v] * coeff[m][u][v]^2.
 // One wave per map over dense [HW] coefficient tiles; lanes stride the tile, fixed-order wave sum.
-__global__ __launch_bounds__(256) void k_weighted_energy(const float* __restrict__ coeff, const float* __restrict__ weights,
+__global__ __launch_bounds__((64 * kReduceWaves)) void k_weighted_energy(const float* __restrict__ coeff, const float* __restrict__ weights,
                                                          long long nmaps, int hw, float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -742,9 +743,9 @@ int dcts_weighted_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t
   basis_forget_range(workspace, workspace_bytes);
   const int hw = (int)(v.HP() * v.WP());
   return coeff_chunks_per_sample(v, chunk, coeff_algo(v), coeff, inner, inner_bytes, stream, [&](int64_t n, long long c0, long long nc) {
-    long long blocks = (nc * 64 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_weighted_energy, dim3((unsigned)blocks), dim3(256), 0, st, coeff, weights, nc, hw, out_nc + n * c_count + c0);
+    long long blocks = (nc + kReduceWaves - 1) / kReduceWaves;  // one wave per map
+    if (blocks > kReduceMaxBlocks) blocks = kReduceMaxBlocks;
+    hipLaunchKernelGGL(k_weighted_energy, dim3((unsigned)blocks), dim3(64 * kReduceWaves), 0, st, coeff, weights, nc, hw, out_nc + n * c_count + c0);
     return (int)hipGetLastError();
   });
 }
@@ -765,7 +766,7 @@ size_t dcts_band_workspace_bytes(int64_t N, int64_t C_count, int64_t H, int64_t 
   // worst case: odd front pad taken. Shapes the fused kernel serves meet the fallback only as row-pitched views.
   const int HP = (int)H + 1, WP = (int)W + 1;
   const long long tile = (long long)HP * WP * 4;
-  const long long cap = (HP <= 65 && WP <= 65) ? (16LL << 20) : (128LL << 20);  // bytes of coefficients per chunk
+  const long long cap = band_chunk_bytes(HP, WP);  // bytes of coefficients per chunk (grid_caps.h)
   long long chunk = cap / tile;
   if (chunk < 1) chunk = 1;
   if (chunk > N * C_count) chunk = N * C_count;
@@ -838,7 +839,7 @@ int dcts_band_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, 
 // The fp32 part is at the head, so that a direct-kernel call keeps its tables where dcts_energy_f32 would: run() is called as
 // dcts_energy_f32 calls it, so the EXISTING basis-table memo (keyed on the caller's workspace pointer, forgotten through
 // dcts_workspace_invalidate[_range]) serves the staged route as well. That is the only host state it touches; none is added.
-constexpr size_t kHalfStageCap = 64u << 20;  // bytes of upcast maps per chunk at most
+// (at most kHalfStageCap bytes of upcast maps per chunk: grid_caps.h)
 
 static bool is_half_dtype(int32_t dtype) { return dtype == DCTS_DTYPE_F16 || dtype == DCTS_DTYPE_BF16; }
 

@@ -29,6 +29,7 @@
 #include "codelet_sizes.h"
 #include "dct_codelets.hpp"
 #include "dcts_internal.h"
+#include "grid_caps.h"
 
 using namespace dctsi;
 
@@ -196,7 +197,7 @@ __global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_band_codelet(Ma
 
 // out[m][b] = sum_i weights[b][i] * coeff[m][i]^2 over dense [hw] coefficient tiles: one wave per map, lanes stride
 // the tile, every coefficient read once for all K bands, fixed-order wave sums
-__global__ __launch_bounds__(256) void k_band_reduce(const float* __restrict__ coeff, const float* __restrict__ weights,
+__global__ __launch_bounds__((64 * kReduceWaves)) void k_band_reduce(const float* __restrict__ coeff, const float* __restrict__ weights,
                                                      long long nmaps, int hw, int K, float* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -267,10 +268,10 @@ int dispatch_band(int HP, int pad, const MapGeom& g, const float* weights, int K
 
 int launch_band_reduce(const float* coeff, const float* weights, long long nmaps, int hw, int K, float* out,
                        hipStream_t st) {
-  long long blocks = (nmaps * 64 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
+  long long blocks = (nmaps + kReduceWaves - 1) / kReduceWaves;  // one wave per map
+  if (blocks > kReduceMaxBlocks) blocks = kReduceMaxBlocks;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_band_reduce, dim3((unsigned)blocks), dim3(256), 0, st, coeff, weights, nmaps, hw, K, out);
+  hipLaunchKernelGGL(k_band_reduce, dim3((unsigned)blocks), dim3(64 * kReduceWaves), 0, st, coeff, weights, nmaps, hw, K, out);
   return (int)hipGetLastError();
 }
 

@@ -25,6 +25,7 @@
 #include "codelet_sizes.h"
 #include "dct_codelets.hpp"
 #include "dcts_internal.h"
+#include "grid_caps.h"
 #include "split_roles.hpp"
 
 using namespace dctsi;
@@ -211,7 +212,6 @@ constexpr int mixed_slab_floats() {
 #undef DCTS_CASE
   return m;
 }
-constexpr int kMixedWaves = 4;
 
 template <int E>
 __device__ __forceinline__ void mixed_group(const MultiItem& item, long long grp, float* my, int lane) {
@@ -262,10 +262,10 @@ __global__ __launch_bounds__((64 * kMixedWaves)) void k_energy_codelet_mixed(Mix
 template <int N>
 struct LaneCfg {
   static constexpr int NN = N * N;
-  static constexpr int G = 64;                         // maps per wave per iteration
+  static constexpr int G = kLaneMultiGroup;            // maps per wave per iteration (grid_caps.h)
   static constexpr int SLAB = (G * NN + 3) / 4 * 4;    // floats
   static constexpr int ITERS = (G * NN / 4 + 63) / 64;  // direct-to-LDS instructions per group
-  static constexpr int WAVES = 2;
+  static constexpr int WAVES = kLaneMultiWaves;
   static_assert(NN % 2 == 1, "lane stride must be odd (bank conflicts) - even tiles use the codelet kernel");
 };
 

@@ -19,6 +19,7 @@
 #include "codelet_schedule.hpp"
 #include "dct_codelets.hpp"
 #include "dcts_internal.h"
+#include "grid_caps.h"
 #include "half_convert.hpp"
 
 using namespace dctsi;
@@ -94,7 +95,7 @@ __global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_energy_half(Hal
 // dst[(m * H + h) * W + w] = float(map m of the slice)[h][w] for the g.nmaps maps of g: one element per thread and step,
 // consecutive threads consecutive elements of a row
 template <int DT>
-__global__ __launch_bounds__(256) void k_upcast_half(HalfGeom g, int H, int W, long long strideH, float* __restrict__ dst) {
+__global__ __launch_bounds__(kUpcastThreads) void k_upcast_half(HalfGeom g, int H, int W, long long strideH, float* __restrict__ dst) {
   const long long hw = (long long)H * W;
   const long long total = g.nmaps * hw;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -134,11 +135,11 @@ int dispatch_half(int N, int dtype, const HalfGeom& g, float* out, hipStream_t s
 int launch_upcast_half(int dtype, const HalfGeom& g, int H, int W, long long strideH, float* dst, hipStream_t st) {
   if (dtype != DCTS_DTYPE_F16 && dtype != DCTS_DTYPE_BF16) return DCTS_E_UNSUPPORTED;
   const long long total = g.nmaps * (long long)H * W;
-  const unsigned blocks = grid_blocks(total, 256, (long long)num_cus() * 32);  // one thread per element and step
+  const unsigned blocks = grid_blocks(total, kUpcastThreads, (long long)num_cus() * kUpcastBlocksPerCu);  // one thread per element and step
   if (dtype == DCTS_DTYPE_F16)
-    hipLaunchKernelGGL(k_upcast_half<DCTS_DTYPE_F16>, dim3(blocks), dim3(256), 0, st, g, H, W, strideH, dst);
+    hipLaunchKernelGGL(k_upcast_half<DCTS_DTYPE_F16>, dim3(blocks), dim3(kUpcastThreads), 0, st, g, H, W, strideH, dst);
   else
-    hipLaunchKernelGGL(k_upcast_half<DCTS_DTYPE_BF16>, dim3(blocks), dim3(256), 0, st, g, H, W, strideH, dst);
+    hipLaunchKernelGGL(k_upcast_half<DCTS_DTYPE_BF16>, dim3(blocks), dim3(kUpcastThreads), 0, st, g, H, W, strideH, dst);
   return (int)hipGetLastError();
 }
 

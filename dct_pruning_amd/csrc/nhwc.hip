@@ -21,6 +21,7 @@
 #include "codelet_schedule.hpp"
 #include "dct_codelets.hpp"
 #include "dcts_internal.h"
+#include "grid_caps.h"
 #include "half_convert.hpp"
 
 using namespace dctsi;
@@ -44,7 +45,7 @@ __device__ __forceinline__ float load_elem(const typename NhwcElem<DT>::type* p)
     return half_to_float<DT>(*p);
 }
 
-constexpr int kLaneWaves = 4;  // waves per workgroup of the lane = channel kernel
+constexpr int kLaneWaves = kNhwcLaneWaves;  // waves per workgroup of the lane = channel kernel (grid_caps.h)
 
 template <int N, int DT>
 __global__ __launch_bounds__(64 * kLaneWaves) void k_nhwc_lane(NhwcGeom g, float* __restrict__ out) {
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(64 * kLaneWaves) void k_nhwc_lane(NhwcGeom g, float
 template <int N>
 struct NhwcBlockCfg {
   using Cfg = CodeletCfg<N>;
-  static constexpr int CB = N <= 16 ? 32 : (N <= 28 ? 16 : 8);
+  static constexpr int CB = nhwc_block_cb(N);  // grid_caps.h: N <= 16 ? 32 : (N <= 28 ? 16 : 8)
   static constexpr int WAVES = CB / Cfg::G;
   static constexpr int THREADS = 64 * WAVES;
   static constexpr int MS = N == 14 ? 239 : N == 16 ? 273 : N == 28 ? 926 : 1060;
@@ -216,7 +217,7 @@ __global__ __launch_bounds__((NhwcBlockCfg<N>::THREADS)) void k_nhwc_block(NhwcG
 // floats per channel: CS = 8 mod 32 puts the staging stores of a half-wave (8 pixels x 4 channels) on 32 distinct banks, and
 // a wave's reads (one channel, consecutive columns) are conflict-free. Each wave picks its map's values of the strip into xr.
 struct NhwcStripCfg {
-  static constexpr int N = 56, CB = 4, R = 8, WAVES = CB, THREADS = 64 * WAVES, CS = 456;
+  static constexpr int N = 56, CB = kNhwcStripCb, R = 8, WAVES = CB, THREADS = 64 * WAVES, CS = 456;
   static constexpr int PSTEP = THREADS / CB;                     // pixels a workgroup loads per step
   static constexpr int STEPS = (R * N + PSTEP - 1) / PSTEP;      // per strip
   static_assert(N % R == 0 && CS >= R * N, "strip geometry");

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "../../include/dctscore.h"
+#include "grid_caps.h"
 
 namespace {
 
@@ -193,13 +194,11 @@ __global__ __launch_bounds__(64) void k_rank(RankGeom g) {
   }
 }
 
-constexpr int kMaxBlocks = 8192;  // grid-stride beyond: 256 CUs x 32 single-wave workgroups
-
 template <int G>
 int launch(RankGeom g, hipStream_t st) {
   constexpr int MPW = 64 / G;
   const int64_t tasks = (g.maps + MPW - 1) / MPW;
-  const int blocks = (int)(tasks < kMaxBlocks ? tasks : kMaxBlocks);
+  const int blocks = (int)(tasks < dctsi::kRankMaxBlocks ? tasks : dctsi::kRankMaxBlocks);  // grid-stride beyond (grid_caps.h)
   const size_t lds = (size_t)MPW * g.slab * sizeof(double);
   hipLaunchKernelGGL((k_rank<G>), dim3(blocks), dim3(64), lds, st, g);
   const hipError_t e = hipGetLastError();

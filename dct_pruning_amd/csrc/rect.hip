@@ -24,6 +24,7 @@
 #include "codelet_sizes.h"
 #include "dct_codelets.hpp"
 
+#include "grid_caps.h"
 #include "rect.h"
 
 // every edge up to 64: the codelet template factorises any N = 2^s * m (m odd: direct, about m^2 / 2 FMAs with literal
@@ -37,8 +38,8 @@
 
 namespace {
 
+using dctsi::kRectWaves;
 using dctsi::RectGeom;
-constexpr int kRectWaves = 4;
 
 __device__ __forceinline__ const float* rect_map_base(const RectGeom& g, long long m) {
   if (g.contiguous) return g.x + ((long long)g.c_begin + m) * g.strideC;
@@ -213,26 +214,12 @@ int dispatch_rect(const RectGeom& g_in, float* out, int store_coeff, hipStream_t
   if (!has_rect(g_in.HP, g_in.WP)) return DCTS_E_UNSUPPORTED;
   RectGeom g = g_in;
   const int edge = g.HP > g.WP ? g.HP : g.WP;
-  // Maps per pass step: floor(64 / WP) with columns as lanes, floor(64 / HP) with rows as lanes. A group is G maps, each pass
-  // taking them in ceil(G / G1) resp. ceil(G / G2) steps: G is chosen to minimise the codelet runs per map (56 x 28: G = 2,
-  // pass 1 once, pass 2 twice; 14 x 20: G = 12, four steps of three and three of four), within the slab a wave may have.
-  g.G1 = 64 / g.WP;
-  g.G2 = 64 / g.HP;
-  g.S = g.WP | 1;             // odd row stride: the row-wise reads of pass 2 hit distinct banks within a map
-  g.map_lds = g.HP * g.S + ((g.HP * g.S) % 2 == 0 ? 1 : 0);
-  // slab per wave: what leaves the LDS room for as many waves as the registers of the size class allow (14 x 20 with a 14 KB
-  // slab of twelve maps ran two workgroups per CU: 28 % of the HBM peak against 45 % with three maps)
-  const int slab_cap = edge <= 16 ? 1536 : (edge <= 32 ? 2304 : 3400);
-  const int gmax = slab_cap / g.map_lds > 0 ? slab_cap / g.map_lds : 1;
-  int best = g.G1 < g.G2 ? g.G1 : g.G2;
-  if (best > gmax) best = gmax;
-  auto runs = [&](int G) { return (G + g.G1 - 1) / g.G1 + (G + g.G2 - 1) / g.G2; };
-  if (!store_coeff)
-    for (int G = best + 1; G <= gmax; ++G)
-      if ((long long)runs(G) * best < (long long)runs(best) * G) best = G;  // strictly fewer runs per map
-  g.G = best;
-  if (g.G1 > g.G) g.G1 = g.G;
-  if (g.G2 > g.G) g.G2 = g.G;
+  const RectGroup rg = rect_group(g.HP, g.WP, store_coeff != 0);  // maps per iteration and pass step, slab geometry (grid_caps.h)
+  g.G = rg.G;
+  g.G1 = rg.G1;
+  g.G2 = rg.G2;
+  g.S = rg.S;
+  g.map_lds = rg.map_lds;
   const bool onestep = g.G1 == g.G && g.G2 == g.G;
   const bool tabulated = rect_tab_1d(g.HP) && rect_tab_1d(g.WP);
   g.scale_e = float(4.0 / (double(g.HP) * double(g.WP)));
@@ -240,7 +227,7 @@ int dispatch_rect(const RectGeom& g_in, float* out, int store_coeff, hipStream_t
   const size_t lds = (size_t)kRectWaves * g.G * g.map_lds * sizeof(float);
   const long long ngroups = (g.nmaps + g.G - 1) / g.G;
   long long blocks = (ngroups + kRectWaves - 1) / kRectWaves;
-  const long long cap = (long long)rect_num_cus() * 64;  // a grid several times the residency (codelet.hip, GRID_WAVES_PER_CU)
+  const long long cap = (long long)rect_num_cus() * kRectBlocksPerCu;  // a grid several times the residency (codelet.hip, GRID_WAVES_PER_CU)
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   static const hipError_t attr_rc = [] {  // four 64 x 65 slabs are 66.6 KB: above the 64 KB a kernel gets without asking
