@@ -6,7 +6,9 @@ DCT-II -> sum of squared coefficients -> per-channel running mean -> .npy score 
 gfx950 HIP kernels behind the C ABI of include/dctscore.h; this package is the host-side
 mirror of the reference's hook / imp_score interface. A second criterion, the HRank feature-map
 rank (rank_nc, imp_score(criterion="rank")), shares everything above the kernel, and so does a third, the per-band
-DCT energy spectrum (band_energy_nc, imp_score(criterion="bands"), bands.py: K frequency bands per map in one pass).
+DCT energy spectrum (band_energy_nc, imp_score(criterion="bands"), bands.py: K frequency bands per map in one pass),
+and a fourth, the spectral entropy of the DCT coefficients (spectral_entropy_nc, imp_score(criterion="entropy")): one
+number per map that does depend on the transform.
 """
 from .ops import (  # noqa: F401
     ALGO_AUTO,
@@ -27,10 +29,12 @@ from .ops import (  # noqa: F401
     energy_nc,
     has_band_kernel,
     has_codelet,
+    has_entropy_kernel,
     has_half_kernel,
     has_nhwc_kernel,
     rank_nc,
+    spectral_entropy_nc,
     weighted_energy_nc,
 )
 
-__all__ = ["energy_nc", "energy_multi", "energy_mixed", "dct2d", "batch_sum", "has_codelet", "weighted_energy_nc", "rank_nc", "band_energy_nc", "has_band_kernel", "has_half_kernel", "has_nhwc_kernel", "ALGO_AUTO", "ALGO_DIRECT", "ALGO_CODELET", "ALGO_SPLIT", "ALGO_PREFETCH", "ALGO_FUSED", "ALGO_PIPE", "ALGO_LANE", "ALGO_TILE2D", "ALGO_RECT"]
+__all__ = ["energy_nc", "energy_multi", "energy_mixed", "dct2d", "batch_sum", "has_codelet", "weighted_energy_nc", "rank_nc", "band_energy_nc", "has_band_kernel", "has_half_kernel", "has_nhwc_kernel", "spectral_entropy_nc", "has_entropy_kernel", "ALGO_AUTO", "ALGO_DIRECT", "ALGO_CODELET", "ALGO_SPLIT", "ALGO_PREFETCH", "ALGO_FUSED", "ALGO_PIPE", "ALGO_LANE", "ALGO_TILE2D", "ALGO_RECT"]

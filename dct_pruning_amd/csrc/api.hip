@@ -8,7 +8,7 @@
 // 2-D DCT-II and the squared coefficients are reduced to one fp32 energy per map.
 //
 // The kernel families are units of their own (codelet.hip, split.hip, fused.hip, fused2.hip, pipe.hip, tile2d.hip,
-// tile2g.hip, rect.hip, rank.hip, band.hip, half.hip). Here:
+// tile2g.hip, rect.hip, rank.hip, band.hip, entropy.hip, half.hip). Here:
 //   k_energy_direct   any (H, W) <= DCTS_MAX_EDGE: separable cosine-matrix transform with
 //                     the basis block staged in LDS; intermediate tile in a caller-provided
 //                     workspace (L2-resident). O(H*W*(H+W)) flops per map: the correct
@@ -831,6 +831,76 @@ int dcts_band_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, 
   if (chunk > c_count) chunk = c_count;
   return coeff_chunks_per_sample(v, chunk, inner_algo, coeff, inner, inner_bytes, stream, [&](int64_t n, long long c0, long long nc) {
     return launch_band_reduce(coeff, weights, nc, hw, K, out_nck + (n * c_count + c0) * K, st);
+  });
+}
+
+// ---- the spectral entropy of every map (entropy.hip) -----------------------------------------------------------------
+// The fused kernel needs no workspace. The fallback lays its workspace out as the band fallback does and chunks by what it
+// is given: [coefficients of a chunk of maps][what the coefficient path needs for that chunk].
+size_t dcts_entropy_workspace_bytes(int64_t N, int64_t C_count, int64_t H, int64_t W) {
+  if (N <= 0 || C_count <= 0 || H <= 0 || W <= 0) return 0;
+  if (H > DCTS_MAX_EDGE || W > DCTS_MAX_EDGE) return 0;
+  // 0 where the fused kernel takes the tile with and without the odd front pad (dense rows)
+  if (has_codelet(H, W) && (H % 2 == 0 || has_codelet(H + 1, W + 1))) return 0;
+  // worst case: odd front pad taken
+  const int HP = (int)H + 1, WP = (int)W + 1;
+  const long long tile = (long long)HP * WP * 4;
+  long long chunk = band_chunk_bytes(HP, WP) / tile;  // bytes of coefficients per chunk (grid_caps.h)
+  if (chunk < 1) chunk = 1;
+  if (chunk > N * C_count) chunk = N * C_count;
+  return align_up(direct_ws(1, HP, WP).off_t + 512 + 2 * (size_t)(chunk * tile), 256);
+}
+
+int dcts_has_entropy_kernel(int64_t H, int64_t W) { return has_codelet(H, W) ? 1 : 0; }
+
+int dcts_spectral_entropy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN,
+                              int64_t strideC, int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count,
+                              int32_t pad_front_if_odd, float* out_nc, void* workspace, size_t workspace_bytes,
+                              void* stream, int32_t algo) {
+  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  if (const int rc = validate(v, {out_nc}, Checks::All)) return rc;
+  const int HP = (int)v.HP(), WP = (int)v.WP();
+  if (algo != DCTS_ALGO_AUTO && algo != DCTS_ALGO_CODELET && algo != DCTS_ALGO_DIRECT) return DCTS_E_UNSUPPORTED;
+  const bool fused_ok = has_codelet(HP, WP) && v.dense_rows();
+  if (algo == DCTS_ALGO_CODELET && !fused_ok) return DCTS_E_UNSUPPORTED;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (fused_ok && algo != DCTS_ALGO_DIRECT) return dispatch_entropy(HP, v.pad(), map_geom(v), out_nc, st);
+
+  // fallback: orthonormal coefficients of a chunk of maps through the coefficient path, then one reduction that reads
+  // each coefficient once
+  if (!workspace) return DCTS_E_WORKSPACE;
+  if (reinterpret_cast<uintptr_t>(workspace) & 15) return DCTS_E_ALIGN;
+  long long chunk = band_fallback_chunk(workspace_bytes, HP, WP);
+  if (chunk < 1) return DCTS_E_WORKSPACE;
+  const long long tile = (long long)HP * WP * 4;
+  char* wsp = reinterpret_cast<char*>(workspace);
+  float* coeff = reinterpret_cast<float*>(wsp);
+  const size_t off_inner = align_up((size_t)(chunk * tile), 256);
+  void* inner = wsp + off_inner;
+  const size_t inner_bytes = workspace_bytes - off_inner;
+  // this call writes coefficients and scratch all over the workspace: no table cached in it survives, and the inner
+  // calls (interior pointer) do not cache theirs
+  basis_forget(workspace);
+  basis_forget_range(workspace, workspace_bytes);
+  const int inner_algo = coeff_algo(v);
+  const int hw = HP * WP;
+  if (chunk >= c_count && (v.contiguous() || inner_algo == DCTS_ALGO_AUTO)) {
+    // whole samples per chunk: (n, channel) jointly, one strided view of x per call
+    const int64_t ns = chunk / c_count;
+    for (int64_t n0 = 0; n0 < N; n0 += ns) {
+      TensorView s = v;
+      s.x = x + n0 * strideN;
+      s.N = (N - n0) < ns ? (N - n0) : ns;
+      int rc = run(true, s, coeff, inner, inner_bytes, stream, inner_algo, /*cache_basis=*/false);
+      if (rc) return rc;
+      rc = launch_entropy_reduce(coeff, s.N * c_count, hw, out_nc + n0 * c_count, st);
+      if (rc) return rc;
+    }
+    return DCTS_OK;
+  }
+  if (chunk > c_count) chunk = c_count;
+  return coeff_chunks_per_sample(v, chunk, inner_algo, coeff, inner, inner_bytes, stream, [&](int64_t n, long long c0, long long nc) {
+    return launch_entropy_reduce(coeff, nc, hw, out_nc + n * c_count + c0, st);
   });
 }
 

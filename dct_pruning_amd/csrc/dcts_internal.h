@@ -151,6 +151,12 @@ int dispatch_band(int HP, int pad, const MapGeom& g, const float* weights, int K
 // fallback reduction: out[m][b] = sum_i weights[b][i] * coeff[m][i]^2 over `nmaps` dense tiles of `hw` coefficients
 int launch_band_reduce(const float* coeff, const float* weights, long long nmaps, int hw, int K, float* out, hipStream_t st);
 
+// ---- entropy.hip: the spectral entropy of every map (dcts_spectral_entropy_f32) ---------------------------------------
+// fused kernel for square tiles with a codelet (HP after the odd pad), dense rows: one launch, no workspace
+int dispatch_entropy(int HP, int pad, const MapGeom& g, float* out, hipStream_t st);
+// fallback reduction: out[m] = entropy of the squares of `nmaps` dense tiles of `hw` coefficients (any common scale)
+int launch_entropy_reduce(const float* coeff, long long nmaps, int hw, float* out, hipStream_t st);
+
 // ---- half.hip: fp16 / bf16 inputs (dcts_energy_typed) -------------------------------------------------------------
 // MapGeom for 2-byte elements (raw bits; the dtype travels beside it). Rows are dense: strideH == W.
 struct HalfGeom {

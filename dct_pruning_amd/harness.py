@@ -31,6 +31,11 @@ Additions (opt-in, results identical on fixed batches):
                       band_score/<net>_limit<L>_<kind><K>/band_*.npy, which bands.collapse turns into imp_*.npy for
                       any band weighting afterwards, on the host (hooks get_feature_hook_bands /
                       get_feature_hook_densenet_bands / get_feature_hook_u2net_input_bands);
+  criterion="entropy" the spectral entropy of every map's DCT coefficients (dcts_spectral_entropy_f32,
+                      ops.spectral_entropy_nc) over the channels and with the odd pad of the DCT hook of that kind: one
+                      number per map, higher = richer, through the same hooks, accumulators, schedules and sharding;
+                      files go to entropy_score/<net>_limit<L>/ent_*.npy (hooks get_feature_hook_entropy /
+                      get_feature_hook_densenet_entropy / get_feature_hook_u2net_input_entropy);
   autocast="fp16" | "bf16"
                       the forward sweeps run under torch.autocast; the hooks hand the tensors to ops.energy_nc in
                       whatever dtype arrives (float16 / bfloat16 maps are scored natively, dcts_energy_typed; a tensor
@@ -54,8 +59,9 @@ from .accumulate import DeviceAccumulator, DeviceBatchAccumulator, HostAccumulat
 _energy_nc = ops.energy_nc
 _rank_nc = ops.rank_nc
 _band_energy_nc = ops.band_energy_nc
+_entropy_nc = ops.spectral_entropy_nc
 
-CRITERIA = ("dct", "rank", "bands")
+CRITERIA = ("dct", "rank", "bands", "entropy")
 AUTOCAST = {"fp16": torch.float16, "bf16": torch.bfloat16}
 
 # the band criterion's partition (K, kind): imp_score(criterion="bands", bands=...) sets it for its hooks
@@ -115,9 +121,21 @@ def _hook_bands(kind, x):
     return _band_piece(x, 0, b, kind == "input")
 
 
+def _hook_entropy(kind, x):
+    """The spectral entropy of every map the DCT hook of that kind scores (same channels, same odd pad)."""
+    b = x.shape[1]
+    if kind == "last12":
+        return _entropy_nc(x, c_begin=b - 12, c_count=12, pad_front_if_odd=True)
+    if kind == "input":
+        return _entropy_nc(x, pad_front_if_odd=True)
+    return _entropy_nc(x)
+
+
 def _hook_score(criterion, kind, x):
     if criterion == "bands":
         return _hook_bands(kind, x)
+    if criterion == "entropy":
+        return _hook_entropy(kind, x)
     return _hook_rank(kind, x) if criterion == "rank" else _hook_energy(kind, x)
 
 
@@ -179,6 +197,23 @@ def get_feature_hook_u2net_input_bands(self, input, output):
     _acc.update(_hook_bands("input", input[0]))
 
 
+def get_feature_hook_entropy(self, input, output):
+    """get_feature_hook with the spectral entropy of every map in place of its DCT energy."""
+    _acc.update(_hook_entropy("full", output))
+
+
+def get_feature_hook_densenet_entropy(self, input, output):
+    """channels [b-12, b), cv2 path (odd front pad)."""
+    _acc.update(_hook_entropy("last12", output))
+
+
+def get_feature_hook_u2net_input_entropy(self, input, output):
+    """scores input[0], cv2 path (odd front pad)."""
+    _acc.update(_hook_entropy("input", input[0]))
+
+
+_ENTROPY_HOOKS = {"full": get_feature_hook_entropy, "last12": get_feature_hook_densenet_entropy,
+                  "input": get_feature_hook_u2net_input_entropy}
 _BAND_HOOKS = {"full": get_feature_hook_bands, "last12": get_feature_hook_densenet_bands,
                "input": get_feature_hook_u2net_input_bands}
 _HOOKS = {"full": get_feature_hook, "last12": get_feature_hook_densenet, "input": get_feature_hook_u2net_input}
@@ -252,6 +287,8 @@ def _file_stem(criterion, stem):
         return "rank_" + stem[len("imp_"):]
     if criterion == "bands":  # imp_conv3 -> band_conv3; U2-Net-p's net.<module path> -> band_net.<module path>
         return "band_" + (stem[len("imp_"):] if stem.startswith("imp_") else stem)
+    if criterion == "entropy":  # the band files' rule: imp_conv3 -> ent_conv3, net.<module path> -> ent_net.<module path>
+        return "ent_" + (stem[len("imp_"):] if stem.startswith("imp_") else stem)
     return stem
 
 
@@ -311,6 +348,8 @@ class _PointHook:
                 e = _rank_nc(x, c_begin=cb, c_count=cc)
             elif self.criterion == "bands":
                 e = _band_piece(x, cb, cc, pad)
+            elif self.criterion == "entropy":
+                e = _entropy_nc(x, c_begin=cb, c_count=cc, pad_front_if_odd=pad)
             else:
                 e = _energy_nc(x, c_begin=cb, c_count=cc, pad_front_if_odd=pad)
             if e.dim() == 3:  # [N, c, K] band energies: the accumulators see the dense [N, c*K] view
@@ -357,7 +396,9 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
     """Counterpart of utils/common.py:367-977. `args` needs .net, .limit (and whatever
     load_data reads when train_loader is None). criterion="rank" scores HRank's feature-map rank instead of the
     DCT energy and writes rank_conv/<net>_limit<L>/rank_*.npy. criterion="bands" with bands=(K, kind) writes the
-    [C, K] band spectrum of every hook point to band_score/<net>_limit<L>_<kind><K>/band_*.npy.
+    [C, K] band spectrum of every hook point to band_score/<net>_limit<L>_<kind><K>/band_*.npy. criterion="entropy"
+    scores the spectral entropy of every map's DCT coefficients and writes entropy_score/<net>_limit<L>/ent_*.npy (all
+    seven nets; not with deferred, autocast or channels_last).
     autocast="fp16" / "bf16" runs the forward sweeps under torch.autocast and scores the half-precision tensors the
     hooks then see as they are (criterion "dct" only, not with deferred).
     channels_last=True converts the net (in place) and every input batch to torch.channels_last; the tensors the hooks
@@ -387,6 +428,8 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
         raise ValueError("imp_score: criterion='rank' has no deferred mode; use single_sweep / accumulate instead")
     if criterion == "rank" and args.net == "u2netp":
         raise ValueError("imp_score: criterion='rank' supports edges up to 64; u2netp (up to 288) is out of scope")
+    if criterion == "entropy" and deferred:
+        raise ValueError("imp_score: criterion='entropy' has no deferred mode; use single_sweep / accumulate instead")
     if criterion == "bands":
         if deferred:
             raise ValueError("imp_score: criterion='bands' has no deferred mode; use single_sweep / accumulate instead")
@@ -399,7 +442,7 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
         # utils/load_models.py:819 calls imp_score from prune_*.py whose parsers define no --limit
         # (AttributeError in the reference as shipped); fall back to importance_generation.py's default
         args.limit = 5
-    root = {"rank": "rank_conv", "bands": "band_score"}.get(criterion, "importance_score")
+    root = {"rank": "rank_conv", "bands": "band_score", "entropy": "entropy_score"}.get(criterion, "importance_score")
     out_dir = root + "/" + args.net + "_limit" + str(args.limit)
     if criterion == "bands":
         out_dir += "_%s%d" % (_band_cfg[1], _band_cfg[0])
@@ -494,7 +537,7 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
                 handler.remove()
                 results[k] = hook.scores()
             else:
-                table = {"rank": _RANK_HOOKS, "bands": _BAND_HOOKS}.get(criterion, _HOOKS)
+                table = {"rank": _RANK_HOOKS, "bands": _BAND_HOOKS, "entropy": _ENTROPY_HOOKS}.get(criterion, _HOOKS)
                 handler = layer.register_forward_hook(table[pt.kind])
                 sweep(net, train_loader, args.limit)
                 handler.remove()

@@ -91,7 +91,7 @@ def compare(a, b):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--imp_score", required=True, help="directory of imp_*.npy files")
+    ap.add_argument("--imp_score", required=True, help="directory of score files: imp_*.npy, rank_*.npy, ent_*.npy (one score per channel) or band_*.npy")
     ap.add_argument("--compress_rate", default="[0.5]*200", help="reference DSL, e.g. '[0.50]*7+[0.95]*5'")
     ap.add_argument("--out", default=None, help="write the masks to this .npz")
     ap.add_argument("--compare", default=None, help="second score directory: report whether the masks match")

@@ -317,6 +317,45 @@ def band_energy_nc(x, weights, c_begin=0, c_count=None, pad_front_if_odd=False, 
     return out
 
 
+def has_entropy_kernel(H, W):
+    """True if the fused spectral-entropy kernel takes an (H, W) tile (sizes after the odd pad)."""
+    return bool(_lib.load().dcts_has_entropy_kernel(H, W))
+
+
+def spectral_entropy_nc(x, c_begin=0, c_count=None, pad_front_if_odd=False, algo=ALGO_AUTO, out=None):
+    """S[n, j] = -sum p ln p over p = c**2 / sum c**2, c = dct_2d(x[n, c_begin+j], norm='ortho') -> [N, c_count] fp32.
+
+    The spectral entropy of every map (dcts_spectral_entropy_f32): how widely its energy spreads over the DCT
+    coefficients, in [0, ln(H' * W')] (natural log; H' = H + 1 for an odd H with pad_front_if_odd). A flat or blob-like
+    map is near 0, a textured one near the top; an all-zero map gives +0.0; scaling a map does not change its value.
+    algo: ALGO_AUTO (fused kernel where it exists, else the fallback), ALGO_CODELET (fused only), ALGO_DIRECT
+    (fallback only). float32 NCHW only; a tensor whose rows are not W-contiguous is copied with .contiguous() first.
+    Enqueues on the current stream of x's device; no synchronisation."""
+    _check_input(x)
+    c_begin, c_count = _slice(x, c_begin, c_count)
+    N, C, H, W = x.shape
+    if out is None:
+        out = torch.empty((N, c_count), dtype=torch.float32, device=x.device)
+    elif out.shape != (N, c_count) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous float32 [N, c_count] tensor on x's device")
+    if x.stride(3) != 1 or x.stride(2) < W:
+        x = x.contiguous()
+    lib = _lib.load()
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    nbytes = lib.dcts_entropy_workspace_bytes(N, c_count, H, W)
+    if nbytes == 0 and (x.stride(2) != W or algo == ALGO_DIRECT):
+        # a fused shape that takes the fallback: sized as the header says, for (H, W + 1)
+        nbytes = lib.dcts_entropy_workspace_bytes(N, c_count, H, W + 1)
+    ws = _workspace(x.device, stream, nbytes) if nbytes else None
+    with torch.cuda.device(x.device):
+        code = lib.dcts_spectral_entropy_f32(
+            x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3), c_begin, c_count,
+            1 if pad_front_if_odd else 0, out.data_ptr(), ws.data_ptr() if nbytes else None, ws.numel() if nbytes else 0,
+            stream, algo)
+    _lib.check(code)
+    return out
+
+
 def rank_nc(x, c_begin=0, c_count=None, out=None):
     """R[n, j] = numerical rank of x[n, c_begin+j] -> [N, c_count] fp32 (exact integers; all-zero map: +0.0).
 

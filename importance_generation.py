@@ -7,12 +7,15 @@ prune_imagenet.py / prune_u2netp.py read through --imp_score. The DCT+score arit
 in libdctscore (HIP, gfx950); a GPU is required.
 
 Extra, opt-in flags: --synthetic (seeded synthetic batches; also lifts the need for a
-checkpoint), --input_size, --seed, --single_sweep, --device_accumulate, --deferred, --criterion {dct,rank}
+checkpoint), --input_size, --seed, --single_sweep, --device_accumulate, --deferred, --criterion {dct,rank,bands,entropy}
 (rank: HRank's feature-map rank instead of the DCT energy, written to rank_conv/<net>_limit<L>/rank_*.npy;
 edges up to 64, so not with --net u2netp, and not with --deferred; bands: the DCT energy of K frequency bands per
 channel, --bands K --band_kind {square,diag}, a [C, K] spectrum per hook point under
 band_score/<net>_limit<L>_<kind><K>/band_*.npy that `python -m dct_pruning_amd.bands` collapses into imp_*.npy for any
-band weighting; not with --deferred), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
+band weighting; not with --deferred; entropy: the spectral entropy of every map's DCT coefficients, one number per
+channel that depends on the transform, written to entropy_score/<net>_limit<L>/ent_*.npy, which
+`python -m dct_pruning_amd.masks` and prune_*.py --imp_score read as they are; every net; not with --deferred,
+--autocast or --channels_last), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
 half-precision feature maps are scored as they are, without an upcast copy; same files, the scores are those of the
 autocast forward pass; --criterion dct only, not with --deferred), --channels_last (the net and its inputs run in
 torch.channels_last and the feature maps are scored in the layout they arrive in, without a transposing copy where a
@@ -49,9 +52,10 @@ def parse_args(argv=None):
     parser.add_argument("--device_accumulate", action="store_true", help="keep the running mean on the GPU")
     parser.add_argument("--deferred", action="store_true",
                         help="single sweep, one scoring launch per tile shape per batch (implies the two above)")
-    parser.add_argument("--criterion", type=str, default="dct", choices=("dct", "rank", "bands"),
+    parser.add_argument("--criterion", type=str, default="dct", choices=("dct", "rank", "bands", "entropy"),
                         help="dct: DCT energy (importance_score/); rank: HRank feature-map rank (rank_conv/); "
-                             "bands: DCT energy per frequency band (band_score/)")
+                             "bands: DCT energy per frequency band (band_score/); "
+                             "entropy: spectral entropy of the DCT coefficients (entropy_score/)")
     parser.add_argument("--bands", type=int, default=4, help="--criterion bands: number of bands K, 1 ... 8")
     parser.add_argument("--band_kind", type=str, default="square", choices=("square", "diag"),
                         help="--criterion bands: L-infinity shells (square) or anti-diagonal stripes (diag)")
@@ -76,6 +80,8 @@ def parse_args(argv=None):
         parser.error("--criterion rank has no --deferred mode (use --single_sweep / --device_accumulate)")
     if args.criterion == "bands" and args.deferred:
         parser.error("--criterion bands has no --deferred mode (use --single_sweep / --device_accumulate)")
+    if args.criterion == "entropy" and args.deferred:
+        parser.error("--criterion entropy has no --deferred mode (use --single_sweep / --device_accumulate)")
     if args.criterion == "bands" and not 1 <= args.bands <= 8:
         parser.error("--bands must be between 1 and 8")
     return args

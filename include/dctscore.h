@@ -47,7 +47,8 @@ extern "C" {
  *    dcts_band_workspace_bytes, dcts_has_band_kernel, DCTS_BAND_MAX) were added to 3 WITHOUT a bump: they are purely
  *    additive, and a library that lacks them fails at symbol lookup. The same holds for the fp16 / bf16 entry points
  *    (dcts_energy_typed, dcts_typed_workspace_bytes, dcts_has_half_kernel, DCTS_DTYPE_*) and for the channels-last ones
- *    (dcts_energy_nhwc, dcts_nhwc_workspace_bytes, dcts_has_nhwc_kernel). */
+ *    (dcts_energy_nhwc, dcts_nhwc_workspace_bytes, dcts_has_nhwc_kernel), and for the spectral-entropy ones
+ *    (dcts_spectral_entropy_f32, dcts_entropy_workspace_bytes, dcts_has_entropy_kernel). */
 #define DCTS_ABI_VERSION 3
 
 enum {
@@ -213,6 +214,40 @@ int dcts_band_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, 
                          int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
                          const float* weights, int32_t K, float* out_nck, void* workspace, size_t workspace_bytes,
                          void* stream, int32_t algo);
+
+/*
+ * The spectral entropy of every map (entropy.hip): how widely a map's energy spreads over its DCT coefficients. With
+ * c = dct_2d(x[n, c_begin+j], norm='ortho') (H' x W' after the optional odd front pad), E = sum c^2 and p = c^2 / E:
+ *
+ *     out_nc[n*c_count + j] = -sum_{p[u,v] > 0} p[u, v] * ln p[u, v]                  [N, c_count] fp32, dense
+ *
+ * Natural logarithm; the value lies in [+0.0, ln(H' * W')] (both ends enforced): near 0 for a flat or blob-like map,
+ * near ln(H' * W') for a textured one. It does not change when the map is scaled. An all-zero map gives exactly +0.0.
+ * All arithmetic is fp32 with the accurate logf, in one pass: e = sum w^2, s = sum w^2 ln w^2 (zero squares add
+ * nothing), H = ln e - s / e, on whatever common scale w the kernel's coefficients have.
+ *   x, strides, c_begin, c_count, pad_front_if_odd    as for dcts_energy_f32; any (H, W) <= DCTS_MAX_EDGE.
+ *   algo       DCTS_ALGO_AUTO     the fused kernel where it exists (square tiles with a codelet,
+ *                                 dcts_has_entropy_kernel(H', W') == 1, rows dense: strideH == W), else the fallback;
+ *              DCTS_ALGO_CODELET  the fused kernel only (DCTS_E_UNSUPPORTED otherwise);
+ *              DCTS_ALGO_DIRECT   the fallback only: coefficients of a chunk of maps through the coefficient path
+ *                                 (dcts_dct2d_f32_ex's kernels) into the workspace, then one reduction that reads
+ *                                 each coefficient once.
+ *   workspace  >= dcts_entropy_workspace_bytes(N, c_count, H, W) bytes, 16-byte aligned; that is 0 where the fused kernel
+ *              takes the shape (with and without the odd pad), and NULL is then fine. A call of such a shape that the
+ *              fused kernel does not take (rows with a pitch, DCTS_ALGO_DIRECT) goes through the fallback: size its
+ *              workspace as for (H, W + 1), which is never fused and never needs less. The fallback chunks by what it is
+ *              given; DCTS_E_WORKSPACE if that is less than the coefficient path's own need plus two tiles.
+ * A map's value depends on that map alone (not on N, the channel slice, its position in a wave, the launch count or the
+ * chunking): bit-reproducible, no atomics. A NaN / Inf map affects only its own output. Only enqueues on `stream`; no
+ * new host state.
+ */
+size_t dcts_entropy_workspace_bytes(int64_t N, int64_t C_count, int64_t H, int64_t W);
+/* 1 if the fused entropy kernel takes an (H, W) tile (sizes AFTER the odd pad). */
+int dcts_has_entropy_kernel(int64_t H, int64_t W);
+int dcts_spectral_entropy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                              int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
+                              int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
+                              float* out_nc, void* workspace, size_t workspace_bytes, void* stream, int32_t algo);
 
 /*
  * dcts_energy_f32 for feature maps of another element type: what a forward pass under autocast hands to a hook.
