@@ -1,6 +1,6 @@
 // api.hip - the C ABI of include/dctscore.h. Every entry point turns its arguments into a TensorView, validate() checks it,
 // choose() names the kernel family that serves it (the only place where a shape becomes a family), and run() packs that family's
-// descriptor and calls its dispatcher (dcts_internal.h, rect.h). Also the kernels that belong to no family.
+// descriptor and calls its dispatcher (dcts_internal.h, rect.h). Host code only: every kernel lives in a unit of its own.
 //
 // Replaces the per-map Python loop of the reference hooks (utils/common.py:262-309):
 //   c = [dct.dct_2d(output[i,j,:,:], norm='ortho') ...]; torch.sum(dct.mul(dct)).item()
@@ -8,11 +8,9 @@
 // 2-D DCT-II and the squared coefficients are reduced to one fp32 energy per map.
 //
 // The kernel families are units of their own (codelet.hip, split.hip, fused.hip, fused2.hip, pipe.hip, tile2d.hip,
-// tile2g.hip, rect.hip, rank.hip, band.hip, entropy.hip, half.hip). Here:
-//   k_energy_direct   any (H, W) <= DCTS_MAX_EDGE: separable cosine-matrix transform with
-//                     the basis block staged in LDS; intermediate tile in a caller-provided
-//                     workspace (L2-resident). O(H*W*(H+W)) flops per map: the correct
-//                     fallback, compute-bound for large tiles.
+// tile2g.hip, rect.hip, rank.hip, band.hip, entropy.hip, half.hip, nhwc.hip, direct.hip: the cosine-matrix fallback for any
+// (H, W) <= DCTS_MAX_EDGE, reduce.hip: batch sum, running mean, weighted reduction). What stays here of the direct family is
+// the memo of its basis tables: which workspace holds which tables is host policy.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -30,258 +28,6 @@
 using namespace dctsi;
 
 namespace {
-
-// ---------------------------------------------------------------------------------------
-// direct family: basis tables + separable transform
-// ---------------------------------------------------------------------------------------
-// Bt[r*n + k] = s_k cos(pi (2r+1) k / (2n)), s_0 = sqrt(1/n), s_k = sqrt(2/n)
-__global__ void k_basis(float* __restrict__ Bt, int n) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n * n) return;
-  const int r = idx / n, k = idx - r * n;
-  const long long num = ((long long)(2 * r + 1) * k) % (4LL * n);
-  const double cv = cospi(double(num) / double(2 * n));
-  const double s = (k == 0) ? sqrt(1.0 / double(n)) : sqrt(2.0 / double(n));
-  Bt[idx] = float(cv * s);
-}
-
-constexpr int kDirectThreads = 256;
-constexpr int kKB = 8;  // output rows per basis block
-
-template <bool STORE_COEFF>
-__global__ __launch_bounds__(kDirectThreads) void k_energy_direct(
-    MapGeom g, int pad, const float* __restrict__ CHt, const float* __restrict__ CWt,
-    float* __restrict__ T, float* __restrict__ out) {
-  const int HP = g.H + pad, WP = g.W + pad;
-  __shared__ __attribute__((aligned(16))) float Bs[DCTS_MAX_EDGE][kKB];
-  __shared__ float red[kDirectThreads / 64];
-  const int tid = threadIdx.x;
-  float* Tm = T + (size_t)blockIdx.x * HP * WP;
-
-  for (long long m = blockIdx.x; m < g.nmaps; m += gridDim.x) {
-    const float* xm = map_base(g, m);
-    // ---- phase 1: Tm[k][c] = sum_r CH[k][r] x'[r][c] --------------------------------
-    for (int k0 = 0; k0 < HP; k0 += kKB) {
-      __syncthreads();
-      for (int i = tid; i < HP * kKB; i += kDirectThreads) {
-        const int r = i / kKB, kk = i - r * kKB;
-        Bs[r][kk] = (k0 + kk < HP) ? CHt[r * HP + k0 + kk] : 0.f;
-      }
-      __syncthreads();
-      for (int c = tid; c < WP; c += kDirectThreads) {
-        float acc[kKB];
-#pragma unroll
-        for (int kk = 0; kk < kKB; ++kk) acc[kk] = 0.f;
-        if (c >= pad) {
-          const float* col = xm + (c - pad);
-          for (int r = pad; r < HP; ++r) {
-            const float xv = col[(long long)(r - pad) * g.strideH];
-            const float4 b0 = *reinterpret_cast<const float4*>(&Bs[r][0]);
-            const float4 b1 = *reinterpret_cast<const float4*>(&Bs[r][4]);
-            acc[0] = fmaf(xv, b0.x, acc[0]);
-            acc[1] = fmaf(xv, b0.y, acc[1]);
-            acc[2] = fmaf(xv, b0.z, acc[2]);
-            acc[3] = fmaf(xv, b0.w, acc[3]);
-            acc[4] = fmaf(xv, b1.x, acc[4]);
-            acc[5] = fmaf(xv, b1.y, acc[5]);
-            acc[6] = fmaf(xv, b1.z, acc[6]);
-            acc[7] = fmaf(xv, b1.w, acc[7]);
-          }
-        }
-#pragma unroll
-        for (int kk = 0; kk < kKB; ++kk)
-          if (k0 + kk < HP) Tm[(k0 + kk) * WP + c] = acc[kk];
-      }
-    }
-    // ---- phase 2: Y[k][l] = sum_c Tm[k][c] CW[l][c]; energy += Y^2 --------------------
-    float e = 0.f;
-    for (int k0 = 0; k0 < HP; k0 += kKB) {
-      __syncthreads();  // also orders phase-1 global stores before these loads (same CU)
-      for (int i = tid; i < WP * kKB; i += kDirectThreads) {
-        const int cc = i / kKB, kk = i - cc * kKB;
-        Bs[cc][kk] = (k0 + kk < HP) ? Tm[(k0 + kk) * WP + cc] : 0.f;
-      }
-      __syncthreads();
-      for (int l = tid; l < WP; l += kDirectThreads) {
-        float acc[kKB];
-#pragma unroll
-        for (int kk = 0; kk < kKB; ++kk) acc[kk] = 0.f;
-        for (int cc = 0; cc < WP; ++cc) {
-          const float wv = CWt[cc * WP + l];
-          const float4 b0 = *reinterpret_cast<const float4*>(&Bs[cc][0]);
-          const float4 b1 = *reinterpret_cast<const float4*>(&Bs[cc][4]);
-          acc[0] = fmaf(wv, b0.x, acc[0]);
-          acc[1] = fmaf(wv, b0.y, acc[1]);
-          acc[2] = fmaf(wv, b0.z, acc[2]);
-          acc[3] = fmaf(wv, b0.w, acc[3]);
-          acc[4] = fmaf(wv, b1.x, acc[4]);
-          acc[5] = fmaf(wv, b1.y, acc[5]);
-          acc[6] = fmaf(wv, b1.z, acc[6]);
-          acc[7] = fmaf(wv, b1.w, acc[7]);
-        }
-#pragma unroll
-        for (int kk = 0; kk < kKB; ++kk) {
-          if (k0 + kk < HP) {
-            if constexpr (STORE_COEFF)
-              out[(m * HP + k0 + kk) * WP + l] = acc[kk];
-            else
-              e = fmaf(acc[kk], acc[kk], e);
-          }
-        }
-      }
-    }
-    if constexpr (!STORE_COEFF) {
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) e += __shfl_down(e, off, 64);
-      __syncthreads();
-      if ((tid & 63) == 0) red[tid >> 6] = e;
-      __syncthreads();
-      if (tid == 0) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < kDirectThreads / 64; ++i) s += red[i];
-        out[m] = s;
-      }
-    }
-  }
-}
-
-// Batch sum over n of E[n][j] for a 32-channel strip per block: kSumSl = 16 n-slices run in parallel
-// (slice s takes n = s, s+16, ...), partials are combined in slice order -> a fixed,
-// launch-independent summation order (bit-reproducible, no atomics).
-constexpr int kSumCh = 32, kSumSl = 16;
-__device__ __forceinline__ float strip_batch_sum(const float* __restrict__ e, long long N,
-                                                 long long C, long long j, int slice,
-                                                 float (*part)[kSumCh]) {
-  float s = 0.f;
-  if (j < C) {
-    long long n = slice;
-    // sixteen loads in flight per lane and round trip (a batch of 256 samples is ONE round trip: the
-    // kernel is pure latency, 3.8 us with four loads per trip); the additions keep their order
-#pragma unroll 1
-    for (; n + 15 * kSumSl < N; n += 16 * kSumSl) {
-      float a[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) a[i] = e[(n + i * kSumSl) * C + j];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s += a[i];
-    }
-#pragma unroll 1
-    for (; n + 3 * kSumSl < N; n += 4 * kSumSl) {
-      const float a0 = e[n * C + j], a1 = e[(n + kSumSl) * C + j];
-      const float a2 = e[(n + 2 * kSumSl) * C + j], a3 = e[(n + 3 * kSumSl) * C + j];
-      s += a0;
-      s += a1;
-      s += a2;
-      s += a3;
-    }
-    for (; n < N; n += kSumSl) s += e[n * C + j];
-  }
-  part[slice][threadIdx.x % kSumCh] = s;
-  __syncthreads();
-  float t = 0.f;
-  if (slice == 0) {
-#pragma unroll
-    for (int i = 0; i < kSumSl; ++i) t += part[i][threadIdx.x % kSumCh];
-  }
-  return t;  // valid in slice 0
-}
-
-// out_c[j] = sum_n e[n*C + j]
-__global__ __launch_bounds__(kSumCh * kSumSl) void k_batch_sum(const float* __restrict__ e, long long N,
-                                                               long long C, float* __restrict__ out_c) {
-  __shared__ float part[kSumSl][kSumCh];
-  const int slice = threadIdx.x / kSumCh;
-  const long long j = (long long)blockIdx.x * kSumCh + threadIdx.x % kSumCh;
-  const float t = strip_batch_sum(e, N, C, j, slice, part);
-  if (slice == 0 && j < C) out_c[j] = t;
-}
-
-// fr[j] <- (fr[j] * total + sum_n e[n*C + j]) / (total + N): the running-mean update of
-// utils/common.py:274-277 fused with the batch sum of :273 (same three fp32 roundings)
-__global__ __launch_bounds__(kSumCh * kSumSl) void k_running_mean(const float* __restrict__ e, long long N,
-                                                                  long long C, float* __restrict__ fr,
-                                                                  float total) {
-  __shared__ float part[kSumSl][kSumCh];
-  const int slice = threadIdx.x / kSumCh;
-  const long long j = (long long)blockIdx.x * kSumCh + threadIdx.x % kSumCh;
-  const float t = strip_batch_sum(e, N, C, j, slice, part);
-  if (slice == 0 && j < C) {
-    const float acc = __fadd_rn(__fmul_rn(fr[j], total), t);
-    fr[j] = __fdiv_rn(acc, __fadd_rn(total, float(N)));
-  }
-}
-
-// the same update for up to kMultiMax hook points in one launch (descriptors by value in the
-// kernel arguments): blockIdx.y = hook point, blockIdx.x = 32-channel strip
-constexpr int kMultiMax = 64;
-struct UpdateBatch {
-  dcts_update_desc d[kMultiMax];
-};
-__global__ __launch_bounds__(kSumCh * kSumSl) void k_running_mean_multi(UpdateBatch b) {
-  __shared__ float part[kSumSl][kSumCh];
-  const dcts_update_desc d = b.d[blockIdx.y];
-  if ((long long)blockIdx.x * kSumCh >= d.C_count) return;  // whole block leaves together
-  const int slice = threadIdx.x / kSumCh;
-  const long long j = (long long)blockIdx.x * kSumCh + threadIdx.x % kSumCh;
-  const float t = strip_batch_sum(d.energy_nc, d.N, d.C_count, j, slice, part);
-  if (slice == 0 && j < d.C_count) {
-    const float acc = __fadd_rn(__fmul_rn(d.feature_result[j], d.total_before), t);
-    d.feature_result[j] = __fdiv_rn(acc, __fadd_rn(d.total_before, float(d.N)));
-  }
-}
-
-// Score variant in the coefficient domain: out[m] = sum_{u,v} weights[u,v] * coeff[m][u][v]^2.
-// One wave per map over dense [HW] coefficient tiles; lanes stride the tile, fixed-order wave sum.
-__global__ __launch_bounds__((64 * kReduceWaves)) void k_weighted_energy(const float* __restrict__ coeff, const float* __restrict__ weights,
-                                                         long long nmaps, int hw, float* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
-  for (long long m = wave; m < nmaps; m += nwaves) {
-    const float* c = coeff + m * hw;
-    float e = 0.f;
-    for (int i = lane; i < hw; i += 64) {
-      const float v = c[i];
-      e = fmaf(weights[i] * v, v, e);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) e += __shfl_down(e, off, 64);
-    if (lane == 0) out[m] = e;
-  }
-}
-
-// PMC calibration aid: streams n floats with the codelet kernels' access width (one dword per
-// lane, consecutive lanes consecutive addresses) so FETCH_SIZE can be compared with a known
-// byte count in this exact pattern (MI355X_MICROARCH.md, HBM section: widths other than
-// 16 B/lane are uncalibrated).
-__global__ __launch_bounds__(256) void k_calib_read(const float* __restrict__ x, long long n,
-                                                    float* __restrict__ sink) {
-  float s = 0.f;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x)
-    s += x[i];
-  if (s == 123456.789f) sink[0] = s;  // keeps the loads alive without a store in practice
-}
-
-// ---------------------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------------------
-constexpr int kDirectGridCap = 512;
-
-struct DirectWs {
-  size_t off_ch, off_cw, off_t, total;
-  int grid;
-};
-DirectWs direct_ws(long long nmaps, int HP, int WP) {
-  DirectWs w;
-  w.grid = (int)(nmaps < kDirectGridCap ? (nmaps > 0 ? nmaps : 1) : kDirectGridCap);
-  w.off_ch = 0;
-  w.off_cw = align_up(w.off_ch + (size_t)HP * HP * 4, 256);
-  w.off_t = align_up(w.off_cw + (size_t)WP * WP * 4, 256);
-  w.total = align_up(w.off_t + (size_t)w.grid * HP * WP * 4, 256);
-  return w;
-}
 
 // ---- one tensor argument set ------------------------------------------------------------------------------------------
 // What an entry point is given for one tensor, and the facts every path derives from it. The derived facts are
@@ -304,6 +50,11 @@ struct TensorView {
   bool dense_maps() const { return dense_square() && contiguous(); }                // and the blocks adjacent: an array of tiles
 };
 
+// the single-tensor entry points' common argument list (x of a 2-byte dtype is tested, never offset: base() is for fp32)
+TensorView view_of(const void* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN, int64_t strideC, int64_t strideH,
+                   int64_t strideW, int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd) {
+  return TensorView{static_cast<const float*>(x), N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+}
 // the list entry points: rows are dense by contract
 TensorView view_of(const dcts_tensor_item& t, int64_t H, int64_t W, int32_t pad_front_if_odd) {
   return TensorView{t.x, t.N, t.C_total, H, W, t.strideN, t.strideC, W, 1, t.c_begin, t.c_count, pad_front_if_odd != 0};
@@ -312,14 +63,17 @@ TensorView view_of(const dcts_shaped_item& it) { return view_of(it.t, it.H, it.W
 
 // The argument checks, in the one order every entry point makes them in. `ptrs`: the other device pointers the call requires
 // (out, weights), tested for NULL and 4-byte alignment together with x. `shape_ok`: the entry point's own shape condition (the
-// band count). The entry points differ only in where they stop:
+// band count). `x_mask`: the alignment of x, 3 or elem_mask() of its dtype. `channels_last`: the stride rule of that layout
+// (pixels at least C_total apart, rows at least W pixels; strideH >= W * strideW without the product) in place of dense NCHW
+// rows. The entry points differ only in where they stop:
 //   Channels  dcts_weighted_energy_f32: its workspace comes next; the first inner coefficient call checks the rest (so a bad
 //             workspace is reported before a bad stride);
 //   Align     the list entry points, per item: an edge beyond DCTS_MAX_EDGE or 2^40 maps is found by the per-tensor call;
 //   All       everything else.
 enum class Checks { Channels, Align, All };
-int validate(const TensorView& v, std::initializer_list<const void*> ptrs, Checks upto, bool shape_ok = true) {
-  bool null = !v.x, misaligned = (reinterpret_cast<uintptr_t>(v.x) & 3) != 0;
+int validate(const TensorView& v, std::initializer_list<const void*> ptrs, Checks upto, bool shape_ok = true, uintptr_t x_mask = 3,
+             bool channels_last = false) {
+  bool null = !v.x, misaligned = (reinterpret_cast<uintptr_t>(v.x) & x_mask) != 0;
   for (const void* p : ptrs) {
     null = null || !p;
     misaligned = misaligned || (reinterpret_cast<uintptr_t>(p) & 3) != 0;
@@ -328,7 +82,7 @@ int validate(const TensorView& v, std::initializer_list<const void*> ptrs, Check
   if (v.N <= 0 || v.C_total <= 0 || v.H <= 0 || v.W <= 0 || !shape_ok) return DCTS_E_SHAPE;
   if (v.c_count <= 0 || v.c_begin < 0 || (int64_t)v.c_begin + v.c_count > v.C_total) return DCTS_E_CHANNELS;
   if (upto == Checks::Channels) return DCTS_OK;
-  if (v.strideW != 1 || v.strideH < v.W) return DCTS_E_STRIDE;
+  if (channels_last ? (v.strideW < v.C_total || v.strideH / v.W < v.strideW) : (v.strideW != 1 || v.strideH < v.W)) return DCTS_E_STRIDE;
   if (misaligned) return DCTS_E_ALIGN;
   if (upto == Checks::Align) return DCTS_OK;
   if (v.HP() > DCTS_MAX_EDGE || v.WP() > DCTS_MAX_EDGE) return DCTS_E_SHAPE;
@@ -347,7 +101,7 @@ RectGeom rect_geom(const TensorView& v) {
 }
 
 // ---- how a shape finds its kernel (DESIGN.md, section of that name) -----------------------------------------------
-// Every way a call can be served. Direct is api.hip's own cosine-matrix kernel, the others are units of their own.
+// Every way a call can be served.
 enum class Family { Direct, Codelet, Lane, CodeletDma, Rect, Split, Fused, Fused2, Pipe, Tile2d, Tile2g, Tile2gPad };
 struct FamilyTraits {
   int (*batch)(int, const TileBatch&, hipStream_t);  // its dispatcher if it takes a TileBatch: dense tensors of one shape as one map index space
@@ -580,18 +334,18 @@ int run(bool store, const TensorView& v, float* out, void* workspace, size_t wor
   float* CHt = reinterpret_cast<float*>(wsp + ws.off_ch);
   float* CWt = reinterpret_cast<float*>(wsp + ws.off_cw);
   float* T = reinterpret_cast<float*>(wsp + ws.off_t);
+  int rc_tables = 0;
   if (!cache_basis || !basis_cached(workspace, stream, HP, WP)) {
     basis_forget_range(workspace, ws.total);  // whatever tables lay in the bytes this call uses are gone
-    hipLaunchKernelGGL(k_basis, dim3((unsigned)((HP * HP + 255) / 256)), dim3(256), 0, st, CHt, HP);
-    hipLaunchKernelGGL(k_basis, dim3((unsigned)((WP * WP + 255) / 256)), dim3(256), 0, st, CWt, WP);
-    if (cache_basis && hipGetLastError() == hipSuccess)
-      basis_remember(workspace, wsp + ws.off_ch, ws.off_t - ws.off_ch, stream, HP, WP);
+    const int rc = launch_basis(CHt, HP, CWt, WP, st);
+    if (cache_basis && rc == hipSuccess) basis_remember(workspace, wsp + ws.off_ch, ws.off_t - ws.off_ch, stream, HP, WP);
+    // (kept as found: a caching call spends the tables' status on the memo; a non-caching one reports it unless the kernel's own is worse)
+    if (!cache_basis) rc_tables = rc;
   } else {
     basis_forget_range(wsp + ws.off_t, ws.total - ws.off_t);  // the T tiles may cover another entry's tables
   }
-  hipLaunchKernelGGL(store ? k_energy_direct<true> : k_energy_direct<false>, dim3((unsigned)ws.grid), dim3(kDirectThreads), 0, st,
-                     g, pad, CHt, CWt, T, out);
-  return (int)hipGetLastError();
+  const int rc = dispatch_direct(store ? 1 : 0, pad, g, ws.grid, CHt, CWt, T, out, st);
+  return rc ? rc : rc_tables;
 }
 
 // ---- the coefficient fallback of the weighted and band entry points ------------------------------------------------
@@ -606,27 +360,98 @@ int coeff_algo(const TensorView& v) {
   return DCTS_ALGO_AUTO;
 }
 
-// Sample by sample, runs of at most `chunk` channels (one strided view of x each): coefficients into `coeff` through the
-// coefficient path (scratch: `inner`), then reduce(n, c0, nc) over the nc tiles just written.
-template <class Reduce>
-int coeff_chunks_per_sample(const TensorView& v, long long chunk, int algo, float* coeff, void* inner, size_t inner_bytes,
-                            void* stream, Reduce reduce) {
-  for (int64_t n = 0; n < v.N; ++n) {
-    for (long long c0 = 0; c0 < v.c_count; c0 += chunk) {
-      const long long nc = (v.c_count - c0) < chunk ? (v.c_count - c0) : chunk;
-      TensorView s = v;
-      s.x = v.x + n * v.strideN;
-      s.N = 1;
-      s.c_begin = (int32_t)(v.c_begin + c0);
-      s.c_count = (int32_t)nc;
-      int rc = run(true, s, coeff, inner, inner_bytes, stream, algo, /*cache_basis=*/false);
-      if (rc) return rc;
-      rc = reduce(n, c0, nc);
-      if (rc) return rc;
-    }
+// The one chunk loop of the weighted, band, entropy and staged paths: f(n0, ns, c0, nc) for samples [n0, n0 + ns), channels
+// [c0, c0 + nc) of the scored slice, at most `chunk` maps each. Whole samples per chunk where the caller says so (chunk >=
+// c_count then), else runs of channels of ONE sample. Which of the two is the caller's rule.
+template <class F>
+int for_chunks(int64_t N, int64_t c_count, long long chunk, bool whole_samples, F f) {
+  if (whole_samples) {
+    const int64_t ns = chunk / c_count;
+    for (int64_t n0 = 0; n0 < N; n0 += ns)
+      if (const int rc = f(n0, (N - n0) < ns ? (N - n0) : ns, (int64_t)0, c_count)) return rc;
+    return DCTS_OK;
   }
+  for (int64_t n = 0; n < N; ++n)
+    for (int64_t c0 = 0; c0 < c_count; c0 += chunk)
+      if (const int rc = f(n, (int64_t)1, c0, (c_count - c0) < chunk ? (c_count - c0) : chunk)) return rc;
   return DCTS_OK;
 }
+
+// A workspace split into [coefficients of `chunk` maps][inner: the scratch the coefficient path may use for them]
+struct CoeffWs {
+  long long chunk;  // maps; < 1: the workspace is too small
+  float* coeff;
+  void* inner;
+  size_t inner_bytes;
+};
+CoeffWs coeff_ws(void* workspace, size_t workspace_bytes, long long chunk, size_t tile) {
+  const size_t off_inner = align_up((size_t)chunk * tile, 256);
+  char* wsp = reinterpret_cast<char*>(workspace);
+  return CoeffWs{chunk, reinterpret_cast<float*>(wsp), wsp + off_inner, workspace_bytes - off_inner};
+}
+
+// Chunk by chunk (one strided view of x each): coefficients into w.coeff through the coefficient path, then reduce(nmaps,
+// first) over the tiles just written; `first` is the index of their first map in the [N, c_count] output.
+template <class Reduce>
+int coeff_chunks(const TensorView& v, const CoeffWs& w, bool whole_samples, int algo, void* workspace, size_t workspace_bytes,
+                 void* stream, Reduce reduce) {
+  // this call writes coefficients and scratch all over the workspace: no table cached in it survives, and the inner calls
+  // (interior pointer, offset depends on the tile shape) do not cache theirs
+  basis_forget(workspace);
+  basis_forget_range(workspace, workspace_bytes);
+  return for_chunks(v.N, v.c_count, w.chunk, whole_samples, [&](int64_t n0, int64_t ns, int64_t c0, int64_t nc) {
+    TensorView s = v;
+    s.x = v.x + n0 * v.strideN;
+    s.N = ns;
+    s.c_begin = (int32_t)(v.c_begin + c0);
+    s.c_count = (int32_t)nc;
+    if (const int rc = run(true, s, w.coeff, w.inner, w.inner_bytes, stream, algo, /*cache_basis=*/false)) return rc;
+    return reduce(ns * nc, n0 * v.c_count + c0);
+  });
+}
+
+// ---- the band / entropy fallback: workspace = [coefficients of a chunk][the same again + coeff_fixed() for the inner call:
+// the direct kernel's tables and T tiles, or leaf tiles of the large-tile kernels] -----------------------------------------
+size_t coeff_fixed(int HP, int WP) { return direct_ws(1, HP, WP).off_t + 512; }
+// what a workspace of that many bytes holds ...
+CoeffWs coeff_layout(void* workspace, size_t workspace_bytes, int HP, int WP) {
+  const size_t tile = (size_t)HP * WP * 4, fixed = coeff_fixed(HP, WP);
+  const long long chunk = workspace_bytes < fixed + 2 * tile ? 0 : (long long)((workspace_bytes - fixed) / (2 * tile));
+  return coeff_ws(workspace, workspace_bytes, chunk, tile);
+}
+// ... and the bytes the size queries ask for: a chunk of band_chunk_bytes() of coefficients (grid_caps.h), the whole call if less
+size_t coeff_layout_bytes(int64_t nmaps, int HP, int WP) {
+  const long long tile = (long long)HP * WP * 4;
+  long long chunk = band_chunk_bytes(HP, WP) / tile;
+  if (chunk < 1) chunk = 1;
+  if (chunk > nmaps) chunk = nmaps;
+  return coeff_fixed(HP, WP) + 2 * (size_t)(chunk * tile);
+}
+// Whole samples per chunk where the chunk holds one and one strided view can cover them, else runs of channels of one sample.
+template <class Reduce>
+int coeff_fallback(const TensorView& v, void* workspace, size_t workspace_bytes, void* stream, Reduce reduce) {
+  const CoeffWs w = coeff_layout(workspace, workspace_bytes, (int)v.HP(), (int)v.WP());
+  if (w.chunk < 1) return DCTS_E_WORKSPACE;
+  const int algo = coeff_algo(v);
+  const bool whole_samples = w.chunk >= v.c_count && (v.contiguous() || algo == DCTS_ALGO_AUTO);
+  return coeff_chunks(v, w, whole_samples, algo, workspace, workspace_bytes, stream, reduce);
+}
+// what the fused band / entropy kernels take, and the algo values those entry points know
+bool fused_ok(const TensorView& v) { return has_codelet(v.HP(), v.WP()) && v.dense_rows(); }
+bool fused_algo(int algo) { return algo == DCTS_ALGO_AUTO || algo == DCTS_ALGO_CODELET || algo == DCTS_ALGO_DIRECT; }
+
+// ---- the weighted path: workspace = [coefficients of a chunk, to 256 bytes][the same again][what the coefficient path needs] --
+size_t weighted_bytes(long long chunk, long long tile, size_t inner) { return 2 * align_up((size_t)(chunk * tile), 256) + inner; }
+// the largest chunk a workspace holds beside `inner_min` bytes for the inner calls (the size query caps it at 256 MiB)
+long long weighted_chunk(size_t workspace_bytes, long long tile, size_t inner_min) {
+  if (workspace_bytes < (size_t)(2 * tile) + inner_min) return 0;
+  long long chunk = (long long)((workspace_bytes - inner_min) / (size_t)(2 * tile));
+  if (chunk >= 1 && align_up((size_t)(chunk * tile), 256) + (size_t)(chunk * tile) > workspace_bytes) --chunk;
+  return chunk;
+}
+
+constexpr bool is_half_dtype(int32_t dtype) { return dtype == DCTS_DTYPE_F16 || dtype == DCTS_DTYPE_BF16; }
+constexpr uintptr_t elem_mask(int32_t dtype) { return dtype == DCTS_DTYPE_F32 ? 3 : 1; }
 
 }  // namespace
 
@@ -676,7 +501,7 @@ int dcts_energy_f32_ex(const float* x, int64_t N, int64_t C_total, int64_t H, in
                        int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
                        float* out_nc, void* workspace, size_t workspace_bytes, void* stream,
                        int32_t algo) {
-  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  const TensorView v = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd);
   return run(false, v, out_nc, workspace, workspace_bytes, stream, algo);
 }
 
@@ -684,7 +509,7 @@ int dcts_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64
                     int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
                     int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd, float* out_nc,
                     void* workspace, size_t workspace_bytes, void* stream) {
-  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  const TensorView v = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd);
   return run(false, v, out_nc, workspace, workspace_bytes, stream, DCTS_ALGO_AUTO);
 }
 
@@ -693,7 +518,7 @@ int dcts_dct2d_f32_ex(const float* x, int64_t N, int64_t C_total, int64_t H, int
                       int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
                       float* out_coeff, void* workspace, size_t workspace_bytes, void* stream,
                       int32_t algo) {
-  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  const TensorView v = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd);
   return run(true, v, out_coeff, workspace, workspace_bytes, stream, algo);
 }
 
@@ -701,77 +526,46 @@ int dcts_dct2d_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_
                    int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
                    int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd, float* out_coeff,
                    void* workspace, size_t workspace_bytes, void* stream) {
-  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  const TensorView v = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd);
   return run(true, v, out_coeff, workspace, workspace_bytes, stream, DCTS_ALGO_AUTO);
 }
 
 size_t dcts_weighted_workspace_bytes(int64_t N, int64_t C_count, int64_t H, int64_t W) {
   if (N <= 0 || C_count <= 0 || H <= 0 || W <= 0) return 0;
-  // coefficients of a chunk of maps + what the coefficient path itself needs for that chunk
-  const int64_t HP = H + 1, WP = W + 1;
-  const long long tile = (long long)HP * WP * 4;
-  long long chunk = (256LL << 20) / tile;  // 256 MiB of coefficients per chunk at most
+  // worst case: odd front pad taken; 256 MiB of coefficients per chunk at most
+  const long long tile = (long long)(H + 1) * (W + 1) * 4;
+  long long chunk = (256LL << 20) / tile;
   if (chunk < 1) chunk = 1;
   if (chunk > N * C_count) chunk = N * C_count;
-  return align_up((size_t)(chunk * tile), 256) + align_up((size_t)(chunk * tile), 256) + dcts_workspace_bytes(N, C_count, H, W);
+  return weighted_bytes(chunk, tile, dcts_workspace_bytes(N, C_count, H, W));
 }
 
 int dcts_weighted_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN,
                              int64_t strideC, int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count,
                              int32_t pad_front_if_odd, const float* weights, float* out_nc, void* workspace,
                              size_t workspace_bytes, void* stream) {
-  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  const TensorView v = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd);
   if (const int rc = validate(v, {out_nc, weights}, Checks::Channels)) return rc;
   if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15)) return workspace ? DCTS_E_ALIGN : DCTS_E_WORKSPACE;
-  const long long tile = (long long)v.HP() * v.WP() * 4;
-  // workspace = [coefficients of a chunk][scratch the coefficient path may use]
-  const size_t inner_min = dcts_workspace_bytes(1, 1, H, W);
-  if (workspace_bytes < (size_t)(2 * tile) + inner_min) return DCTS_E_WORKSPACE;
-  long long chunk = (long long)((workspace_bytes - inner_min) / (size_t)(2 * tile));
+  const long long tile = (long long)v.HP() * v.WP() * 4;  // (the edges are checked by the first inner call, after the workspace)
+  const long long chunk = weighted_chunk(workspace_bytes, tile, dcts_workspace_bytes(1, 1, H, W));
   if (chunk < 1) return DCTS_E_WORKSPACE;
-  const size_t off_inner = align_up((size_t)(chunk * tile), 256);
-  if (off_inner + (size_t)(chunk * tile) > workspace_bytes) --chunk;
-  if (chunk < 1) return DCTS_E_WORKSPACE;
-  char* wsp = reinterpret_cast<char*>(workspace);
-  float* coeff = reinterpret_cast<float*>(wsp);
-  void* inner = wsp + align_up((size_t)(chunk * tile), 256);
-  const size_t inner_bytes = workspace_bytes - align_up((size_t)(chunk * tile), 256);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // this call writes coefficients and scratch all over the workspace: no table cached in it survives, and the
-  // inner calls (interior pointer, offset depends on the tile shape) do not cache theirs
-  basis_forget(workspace);
-  basis_forget_range(workspace, workspace_bytes);
+  const CoeffWs w = coeff_ws(workspace, workspace_bytes, chunk, (size_t)tile);
   const int hw = (int)(v.HP() * v.WP());
-  return coeff_chunks_per_sample(v, chunk, coeff_algo(v), coeff, inner, inner_bytes, stream, [&](int64_t n, long long c0, long long nc) {
-    long long blocks = (nc + kReduceWaves - 1) / kReduceWaves;  // one wave per map
-    if (blocks > kReduceMaxBlocks) blocks = kReduceMaxBlocks;
-    hipLaunchKernelGGL(k_weighted_energy, dim3((unsigned)blocks), dim3(64 * kReduceWaves), 0, st, coeff, weights, nc, hw, out_nc + n * c_count + c0);
-    return (int)hipGetLastError();
+  // always sample by sample
+  return coeff_chunks(v, w, /*whole_samples=*/false, coeff_algo(v), workspace, workspace_bytes, stream, [&](int64_t nmaps, int64_t first) {
+    return launch_weighted_reduce(w.coeff, weights, nmaps, hw, out_nc + first, st);
   });
 }
 
 // ---- K weighted energies per map (band.hip) ------------------------------------------------------------------------
-// Fallback workspace: [coefficients of a chunk of maps][what the coefficient path needs for that chunk: the direct
-// kernel's tables and T tiles, or leaf tiles of the large-tile kernels]. Both parts are at most align(chunk * tile).
-static long long band_fallback_chunk(size_t workspace_bytes, int HP, int WP) {
-  const size_t tile = (size_t)HP * WP * 4;
-  const size_t fixed = direct_ws(1, HP, WP).off_t + 512;
-  if (workspace_bytes < fixed + 2 * tile) return 0;
-  return (long long)((workspace_bytes - fixed) / (2 * tile));
-}
-
 size_t dcts_band_workspace_bytes(int64_t N, int64_t C_count, int64_t H, int64_t W, int32_t K) {
   if (N <= 0 || C_count <= 0 || H <= 0 || W <= 0 || K < 1 || K > DCTS_BAND_MAX) return 0;
   if (H + 1 > DCTS_MAX_EDGE + 1 || W + 1 > DCTS_MAX_EDGE + 1) return 0;
   // worst case: odd front pad taken. Shapes the fused kernel serves meet the fallback only as row-pitched views.
   const int HP = (int)H + 1, WP = (int)W + 1;
-  const long long tile = (long long)HP * WP * 4;
-  const long long cap = band_chunk_bytes(HP, WP);  // bytes of coefficients per chunk (grid_caps.h)
-  long long chunk = cap / tile;
-  if (chunk < 1) chunk = 1;
-  if (chunk > N * C_count) chunk = N * C_count;
-  const size_t fallback = direct_ws(1, HP, WP).off_t + 512 + 2 * (size_t)(chunk * tile);
-  const size_t table = band_table_bytes(HP, WP, K);
+  const size_t fallback = coeff_layout_bytes(N * C_count, HP, WP), table = band_table_bytes(HP, WP, K);
   return align_up(fallback > table ? fallback : table, 256);
 }
 
@@ -781,74 +575,33 @@ int dcts_band_energy_f32(const float* x, int64_t N, int64_t C_total, int64_t H, 
                          int64_t strideC, int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count,
                          int32_t pad_front_if_odd, const float* weights, int32_t K, float* out_nck, void* workspace,
                          size_t workspace_bytes, void* stream, int32_t algo) {
-  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  const TensorView v = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd);
   if (const int rc = validate(v, {out_nck, weights}, Checks::All, /*shape_ok=*/K >= 1 && K <= DCTS_BAND_MAX)) return rc;
   const int HP = (int)v.HP(), WP = (int)v.WP();
-  if (algo != DCTS_ALGO_AUTO && algo != DCTS_ALGO_CODELET && algo != DCTS_ALGO_DIRECT) return DCTS_E_UNSUPPORTED;
-  const bool fused_ok = has_codelet(HP, WP) && v.dense_rows();
-  if (algo == DCTS_ALGO_CODELET && !fused_ok) return DCTS_E_UNSUPPORTED;
+  if (!fused_algo(algo) || (algo == DCTS_ALGO_CODELET && !fused_ok(v))) return DCTS_E_UNSUPPORTED;
   if (!workspace) return DCTS_E_WORKSPACE;
   if (reinterpret_cast<uintptr_t>(workspace) & 15) return DCTS_E_ALIGN;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-
-  if (fused_ok && algo != DCTS_ALGO_DIRECT) {
+  if (fused_ok(v) && algo != DCTS_ALGO_DIRECT) {
     const size_t table_bytes = band_table_bytes(HP, WP, K);
     if (workspace_bytes < table_bytes) return DCTS_E_WORKSPACE;
     basis_forget_range(workspace, table_bytes);  // the table overwrites whatever basis tables lay there
     return dispatch_band(HP, v.pad(), map_geom(v), weights, K, reinterpret_cast<float*>(workspace), out_nck, st);
   }
-
-  // fallback: coefficients of a chunk of maps through the coefficient path, then one reduction that reads each
-  // coefficient once for all K bands
-  long long chunk = band_fallback_chunk(workspace_bytes, HP, WP);
-  if (chunk < 1) return DCTS_E_WORKSPACE;
-  const long long tile = (long long)HP * WP * 4;
-  char* wsp = reinterpret_cast<char*>(workspace);
-  float* coeff = reinterpret_cast<float*>(wsp);
-  const size_t off_inner = align_up((size_t)(chunk * tile), 256);
-  void* inner = wsp + off_inner;
-  const size_t inner_bytes = workspace_bytes - off_inner;
-  // this call writes coefficients and scratch all over the workspace: no table cached in it survives, and the inner
-  // calls (interior pointer) do not cache theirs
-  basis_forget(workspace);
-  basis_forget_range(workspace, workspace_bytes);
-  const int inner_algo = coeff_algo(v);
-  const int hw = HP * WP;
-  if (chunk >= c_count && (v.contiguous() || inner_algo == DCTS_ALGO_AUTO)) {
-    // whole samples per chunk: (n, channel) jointly, one strided view of x per call
-    const int64_t ns = chunk / c_count;
-    for (int64_t n0 = 0; n0 < N; n0 += ns) {
-      TensorView s = v;
-      s.x = x + n0 * strideN;
-      s.N = (N - n0) < ns ? (N - n0) : ns;
-      int rc = run(true, s, coeff, inner, inner_bytes, stream, inner_algo, /*cache_basis=*/false);
-      if (rc) return rc;
-      rc = launch_band_reduce(coeff, weights, s.N * c_count, hw, K, out_nck + n0 * c_count * K, st);
-      if (rc) return rc;
-    }
-    return DCTS_OK;
-  }
-  if (chunk > c_count) chunk = c_count;
-  return coeff_chunks_per_sample(v, chunk, inner_algo, coeff, inner, inner_bytes, stream, [&](int64_t n, long long c0, long long nc) {
-    return launch_band_reduce(coeff, weights, nc, hw, K, out_nck + (n * c_count + c0) * K, st);
+  // fallback: one reduction per chunk that reads each coefficient once for all K bands
+  return coeff_fallback(v, workspace, workspace_bytes, stream, [&](int64_t nmaps, int64_t first) {
+    return launch_band_reduce(reinterpret_cast<float*>(workspace), weights, nmaps, HP * WP, K, out_nck + first * K, st);
   });
 }
 
 // ---- the spectral entropy of every map (entropy.hip) -----------------------------------------------------------------
-// The fused kernel needs no workspace. The fallback lays its workspace out as the band fallback does and chunks by what it
-// is given: [coefficients of a chunk of maps][what the coefficient path needs for that chunk].
+// The fused kernel needs no workspace; the fallback is the band fallback with another reduction.
 size_t dcts_entropy_workspace_bytes(int64_t N, int64_t C_count, int64_t H, int64_t W) {
   if (N <= 0 || C_count <= 0 || H <= 0 || W <= 0) return 0;
   if (H > DCTS_MAX_EDGE || W > DCTS_MAX_EDGE) return 0;
   // 0 where the fused kernel takes the tile with and without the odd front pad (dense rows)
   if (has_codelet(H, W) && (H % 2 == 0 || has_codelet(H + 1, W + 1))) return 0;
-  // worst case: odd front pad taken
-  const int HP = (int)H + 1, WP = (int)W + 1;
-  const long long tile = (long long)HP * WP * 4;
-  long long chunk = band_chunk_bytes(HP, WP) / tile;  // bytes of coefficients per chunk (grid_caps.h)
-  if (chunk < 1) chunk = 1;
-  if (chunk > N * C_count) chunk = N * C_count;
-  return align_up(direct_ws(1, HP, WP).off_t + 512 + 2 * (size_t)(chunk * tile), 256);
+  return align_up(coeff_layout_bytes(N * C_count, (int)H + 1, (int)W + 1), 256);  // worst case: odd front pad taken
 }
 
 int dcts_has_entropy_kernel(int64_t H, int64_t W) { return has_codelet(H, W) ? 1 : 0; }
@@ -857,50 +610,17 @@ int dcts_spectral_entropy_f32(const float* x, int64_t N, int64_t C_total, int64_
                               int64_t strideC, int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count,
                               int32_t pad_front_if_odd, float* out_nc, void* workspace, size_t workspace_bytes,
                               void* stream, int32_t algo) {
-  const TensorView v{x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd != 0};
+  const TensorView v = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd);
   if (const int rc = validate(v, {out_nc}, Checks::All)) return rc;
   const int HP = (int)v.HP(), WP = (int)v.WP();
-  if (algo != DCTS_ALGO_AUTO && algo != DCTS_ALGO_CODELET && algo != DCTS_ALGO_DIRECT) return DCTS_E_UNSUPPORTED;
-  const bool fused_ok = has_codelet(HP, WP) && v.dense_rows();
-  if (algo == DCTS_ALGO_CODELET && !fused_ok) return DCTS_E_UNSUPPORTED;
+  if (!fused_algo(algo) || (algo == DCTS_ALGO_CODELET && !fused_ok(v))) return DCTS_E_UNSUPPORTED;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (fused_ok && algo != DCTS_ALGO_DIRECT) return dispatch_entropy(HP, v.pad(), map_geom(v), out_nc, st);
-
-  // fallback: orthonormal coefficients of a chunk of maps through the coefficient path, then one reduction that reads
-  // each coefficient once
+  if (fused_ok(v) && algo != DCTS_ALGO_DIRECT) return dispatch_entropy(HP, v.pad(), map_geom(v), out_nc, st);
+  // fallback: one reduction per chunk that reads each coefficient once
   if (!workspace) return DCTS_E_WORKSPACE;
   if (reinterpret_cast<uintptr_t>(workspace) & 15) return DCTS_E_ALIGN;
-  long long chunk = band_fallback_chunk(workspace_bytes, HP, WP);
-  if (chunk < 1) return DCTS_E_WORKSPACE;
-  const long long tile = (long long)HP * WP * 4;
-  char* wsp = reinterpret_cast<char*>(workspace);
-  float* coeff = reinterpret_cast<float*>(wsp);
-  const size_t off_inner = align_up((size_t)(chunk * tile), 256);
-  void* inner = wsp + off_inner;
-  const size_t inner_bytes = workspace_bytes - off_inner;
-  // this call writes coefficients and scratch all over the workspace: no table cached in it survives, and the inner
-  // calls (interior pointer) do not cache theirs
-  basis_forget(workspace);
-  basis_forget_range(workspace, workspace_bytes);
-  const int inner_algo = coeff_algo(v);
-  const int hw = HP * WP;
-  if (chunk >= c_count && (v.contiguous() || inner_algo == DCTS_ALGO_AUTO)) {
-    // whole samples per chunk: (n, channel) jointly, one strided view of x per call
-    const int64_t ns = chunk / c_count;
-    for (int64_t n0 = 0; n0 < N; n0 += ns) {
-      TensorView s = v;
-      s.x = x + n0 * strideN;
-      s.N = (N - n0) < ns ? (N - n0) : ns;
-      int rc = run(true, s, coeff, inner, inner_bytes, stream, inner_algo, /*cache_basis=*/false);
-      if (rc) return rc;
-      rc = launch_entropy_reduce(coeff, s.N * c_count, hw, out_nc + n0 * c_count, st);
-      if (rc) return rc;
-    }
-    return DCTS_OK;
-  }
-  if (chunk > c_count) chunk = c_count;
-  return coeff_chunks_per_sample(v, chunk, inner_algo, coeff, inner, inner_bytes, stream, [&](int64_t n, long long c0, long long nc) {
-    return launch_entropy_reduce(coeff, nc, hw, out_nc + n * c_count + c0, st);
+  return coeff_fallback(v, workspace, workspace_bytes, stream, [&](int64_t nmaps, int64_t first) {
+    return launch_entropy_reduce(reinterpret_cast<float*>(workspace), nmaps, HP * WP, out_nc + first, st);
   });
 }
 
@@ -910,9 +630,6 @@ int dcts_spectral_entropy_f32(const float* x, int64_t N, int64_t C_total, int64_
 // dcts_energy_f32 calls it, so the EXISTING basis-table memo (keyed on the caller's workspace pointer, forgotten through
 // dcts_workspace_invalidate[_range]) serves the staged route as well. That is the only host state it touches; none is added.
 // (at most kHalfStageCap bytes of upcast maps per chunk: grid_caps.h)
-
-static bool is_half_dtype(int32_t dtype) { return dtype == DCTS_DTYPE_F16 || dtype == DCTS_DTYPE_BF16; }
-
 size_t dcts_typed_workspace_bytes(int32_t dtype, int64_t N, int64_t C_count, int64_t H, int64_t W) {
   if (dtype == DCTS_DTYPE_F32) return dcts_workspace_bytes(N, C_count, H, W);
   if (!is_half_dtype(dtype) || N <= 0 || C_count <= 0 || H <= 0 || W <= 0) return 0;
@@ -933,26 +650,15 @@ int dcts_energy_typed(const void* x, int32_t dtype, int64_t N, int64_t C_total, 
     return dcts_energy_f32(reinterpret_cast<const float*>(x), N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin,
                            c_count, pad_front_if_odd, out_nc, workspace, workspace_bytes, stream);
   if (!is_half_dtype(dtype)) return DCTS_E_UNSUPPORTED;
-  // the checks of validate(), in its order, with the element size in the alignment test
-  if (!x || !out_nc) return DCTS_E_NULL;
-  if (N <= 0 || C_total <= 0 || H <= 0 || W <= 0) return DCTS_E_SHAPE;
-  if (c_count <= 0 || c_begin < 0 || (int64_t)c_begin + c_count > C_total) return DCTS_E_CHANNELS;
-  if (strideW != 1 || strideH < W) return DCTS_E_STRIDE;
-  if ((reinterpret_cast<uintptr_t>(x) & 1) || (reinterpret_cast<uintptr_t>(out_nc) & 3)) return DCTS_E_ALIGN;
-  const int pad = (pad_front_if_odd && (H % 2 != 0)) ? 1 : 0;
-  if (H + pad > DCTS_MAX_EDGE || W + pad > DCTS_MAX_EDGE) return DCTS_E_SHAPE;
-  if (N * (int64_t)c_count >= (1LL << 40)) return DCTS_E_SHAPE;
+  const TensorView v = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, pad_front_if_odd);
+  if (const int rc = validate(v, {out_nc}, Checks::All, true, elem_mask(dtype))) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const uint16_t* xh = reinterpret_cast<const uint16_t*>(x);
-  const bool contiguous = N == 1 || strideN == (int64_t)c_count * strideC;
-
-  if (has_half(H, W) && pad == 0 && strideH == W) {
-    const HalfGeom g{xh, N * (int64_t)c_count, strideN, strideC, c_count, c_begin, contiguous ? 1 : 0};
-    return dispatch_half((int)H, dtype, g, out_nc, st);
-  }
+  if (has_half(H, W) && v.pad() == 0 && strideH == W)
+    return dispatch_half((int)H, dtype, HalfGeom{xh, v.nmaps(), strideN, strideC, c_count, c_begin, v.contiguous() ? 1 : 0}, out_nc, st);
 
   // staged: upcast a chunk of maps into the workspace, score it through the fp32 path under AUTO. Whole samples per chunk
-  // where the workspace holds one, else runs of channels of one sample (as the band fallback chunks).
+  // where the workspace holds one, else runs of channels of one sample.
   if (!workspace) return DCTS_E_WORKSPACE;
   if (reinterpret_cast<uintptr_t>(workspace) & 15) return DCTS_E_ALIGN;
   const size_t map = (size_t)H * W * 4;
@@ -965,25 +671,12 @@ int dcts_energy_typed(const void* x, int32_t dtype, int64_t N, int64_t C_total, 
   float* stage = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + inner_bytes);
   void* inner = inner_bytes ? workspace : nullptr;
   basis_forget_range(stage, (size_t)chunk * map);  // the upcast maps overwrite whatever tables lay there
-  auto score = [&](int64_t n0, int64_t ns, int32_t c0, int32_t nc) -> int {
-    // samples [n0, n0 + ns), channels [c_begin + c0, c_begin + c0 + nc) of x
-    const HalfGeom g{xh + n0 * strideN, ns * (int64_t)nc, strideN, strideC, nc, c_begin + c0,
-                     (ns == 1 || strideN == (int64_t)nc * strideC) ? 1 : 0};
-    int rc = launch_upcast_half(dtype, g, (int)H, (int)W, strideH, stage, st);
-    if (rc) return rc;
-    const TensorView v{stage, ns, nc, H, W, (int64_t)nc * H * W, H * W, W, 1, 0, nc, pad_front_if_odd != 0};
-    return run(false, v, out_nc + n0 * c_count + c0, inner, inner_bytes, stream, DCTS_ALGO_AUTO);
-  };
-  if (chunk >= c_count) {
-    const int64_t ns = chunk / c_count;
-    for (int64_t n0 = 0; n0 < N; n0 += ns)
-      if (const int rc = score(n0, (N - n0) < ns ? (N - n0) : ns, 0, c_count)) return rc;
-    return DCTS_OK;
-  }
-  for (int64_t n = 0; n < N; ++n)
-    for (int64_t c0 = 0; c0 < c_count; c0 += chunk)
-      if (const int rc = score(n, 1, (int32_t)c0, (int32_t)((c_count - c0) < chunk ? (c_count - c0) : chunk))) return rc;
-  return DCTS_OK;
+  return for_chunks(N, c_count, chunk, /*whole_samples=*/chunk >= c_count, [&](int64_t n0, int64_t ns, int64_t c0, int64_t nc) -> int {
+    const HalfGeom g{xh + n0 * strideN, ns * nc, strideN, strideC, (int)nc, (int)(c_begin + c0), (ns == 1 || strideN == nc * strideC) ? 1 : 0};
+    if (const int rc = launch_upcast_half(dtype, g, (int)H, (int)W, strideH, stage, st)) return rc;
+    const TensorView s{stage, ns, nc, H, W, nc * H * W, H * W, W, 1, 0, (int32_t)nc, pad_front_if_odd != 0};
+    return run(false, s, out_nc + n0 * c_count + c0, inner, inner_bytes, stream, DCTS_ALGO_AUTO);
+  });
 }
 
 // ---- channels-last maps (nhwc.hip) ------------------------------------------------------------------------------------
@@ -993,43 +686,26 @@ int dcts_has_nhwc_kernel(int64_t H, int64_t W) { return has_nhwc(H, W) ? 1 : 0; 
 size_t dcts_nhwc_workspace_bytes(int32_t, int64_t, int64_t, int64_t, int64_t) { return 0; }
 
 int dcts_energy_nhwc(const void* x, int32_t dtype, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN,
-                     int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count, float* out_nc, void* workspace,
-                     size_t workspace_bytes, void* stream) {
-  (void)workspace;
-  (void)workspace_bytes;
+                     int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count, float* out_nc, void*, size_t, void* stream) {
   if (dtype != DCTS_DTYPE_F32 && !is_half_dtype(dtype)) return DCTS_E_UNSUPPORTED;
-  // the checks of dcts_energy_typed, in its order; the stride rules are those of the channels-last layout
-  if (!x || !out_nc) return DCTS_E_NULL;
-  if (N <= 0 || C_total <= 0 || H <= 0 || W <= 0) return DCTS_E_SHAPE;
-  if (c_count <= 0 || c_begin < 0 || (int64_t)c_begin + c_count > C_total) return DCTS_E_CHANNELS;
-  if (strideW < C_total || strideH / W < strideW) return DCTS_E_STRIDE;  // strideH >= W * strideW without the product
-  const uintptr_t elem_mask = dtype == DCTS_DTYPE_F32 ? 3 : 1;
-  if ((reinterpret_cast<uintptr_t>(x) & elem_mask) || (reinterpret_cast<uintptr_t>(out_nc) & 3)) return DCTS_E_ALIGN;
-  if (H > DCTS_MAX_EDGE || W > DCTS_MAX_EDGE) return DCTS_E_SHAPE;
-  if (N * (int64_t)c_count >= (1LL << 40)) return DCTS_E_SHAPE;
+  const TensorView v = view_of(x, N, C_total, H, W, strideN, /*strideC=*/1, strideH, strideW, c_begin, c_count, /*pad_front_if_odd=*/0);
+  if (const int rc = validate(v, {out_nc}, Checks::All, true, elem_mask(dtype), /*channels_last=*/true)) return rc;
   if (!has_nhwc(H, W)) return DCTS_E_UNSUPPORTED;  // the caller's copy into the NCHW layout stays the caller's
-  const NhwcGeom g{x, N, strideN, strideH, strideW, c_begin, c_count};
-  return dispatch_nhwc((int)H, dtype, g, out_nc, reinterpret_cast<hipStream_t>(stream));
+  return dispatch_nhwc((int)H, dtype, NhwcGeom{x, N, strideN, strideH, strideW, c_begin, c_count}, out_nc, reinterpret_cast<hipStream_t>(stream));
 }
 
 int dcts_batch_sum_f32(const float* energy_nc, int64_t N, int64_t C_count, float* out_c,
                        void* stream) {
   if (!energy_nc || !out_c) return DCTS_E_NULL;
   if (N <= 0 || C_count <= 0) return DCTS_E_SHAPE;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_batch_sum, dim3((unsigned)((C_count + kSumCh - 1) / kSumCh)), dim3(kSumCh * kSumSl), 0, st,
-                     energy_nc, (long long)N, (long long)C_count, out_c);
-  return (int)hipGetLastError();
+  return launch_batch_sum(energy_nc, N, C_count, out_c, reinterpret_cast<hipStream_t>(stream));
 }
 
 int dcts_running_mean_update_f32(const float* energy_nc, int64_t N, int64_t C_count,
                                  float* feature_result, float total_before, void* stream) {
   if (!energy_nc || !feature_result) return DCTS_E_NULL;
   if (N <= 0 || C_count <= 0) return DCTS_E_SHAPE;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_running_mean, dim3((unsigned)((C_count + kSumCh - 1) / kSumCh)), dim3(kSumCh * kSumSl), 0, st,
-                     energy_nc, (long long)N, (long long)C_count, feature_result, total_before);
-  return (int)hipGetLastError();
+  return launch_running_mean(energy_nc, N, C_count, feature_result, total_before, reinterpret_cast<hipStream_t>(stream));
 }
 
 int dcts_energy_multi_f32(const dcts_tensor_item* items, int32_t count, int64_t H, int64_t W,
@@ -1175,21 +851,18 @@ int dcts_running_mean_update_multi_f32(const dcts_update_desc* descs, int32_t co
   if (!descs) return DCTS_E_NULL;
   if (count <= 0) return DCTS_E_SHAPE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int rc = DCTS_OK;  // of the last launch that failed: every chunk is launched (and checked only when its turn comes)
   for (int32_t i0 = 0; i0 < count; i0 += kMultiMax) {
     const int n = (count - i0) < kMultiMax ? (count - i0) : kMultiMax;
-    UpdateBatch b;
     int64_t cmax = 0;
-    for (int i = 0; i < n; ++i) {
-      b.d[i] = descs[i0 + i];
-      if (!b.d[i].energy_nc || !b.d[i].feature_result) return DCTS_E_NULL;
-      if (b.d[i].N <= 0 || b.d[i].C_count <= 0) return DCTS_E_SHAPE;
-      if (b.d[i].C_count > cmax) cmax = b.d[i].C_count;
+    for (const dcts_update_desc* d = descs + i0; d < descs + i0 + n; ++d) {
+      if (!d->energy_nc || !d->feature_result) return DCTS_E_NULL;
+      if (d->N <= 0 || d->C_count <= 0) return DCTS_E_SHAPE;
+      if (d->C_count > cmax) cmax = d->C_count;
     }
-    for (int i = n; i < kMultiMax; ++i) b.d[i] = b.d[0];
-    hipLaunchKernelGGL(k_running_mean_multi, dim3((unsigned)((cmax + kSumCh - 1) / kSumCh), (unsigned)n),
-                       dim3(kSumCh * kSumSl), 0, st, b);
+    if (const int r = launch_running_mean_multi(descs + i0, n, cmax, st)) rc = r;
   }
-  return (int)hipGetLastError();
+  return rc;
 }
 
 #ifdef DCTS_FUSED_STAMPS
@@ -1205,9 +878,7 @@ int dcts_debug_fused_stamps(unsigned long long* host_out /*[16][16]*/, int reset
 int dcts_debug_stream_read_f32(const float* x, int64_t n, float* sink, void* stream) {
   if (!x || !sink) return DCTS_E_NULL;
   if (n <= 0) return DCTS_E_SHAPE;
-  hipLaunchKernelGGL(k_calib_read, dim3(256 * 32), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x,
-                     (long long)n, sink);
-  return (int)hipGetLastError();
+  return launch_stream_read(x, n, sink, reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -8,6 +8,8 @@
 
 #include "codelet_sizes.h"
 
+struct dcts_update_desc;  // include/dctscore.h
+
 namespace dctsi {
 
 struct MapGeom {
@@ -142,6 +144,28 @@ int dispatch_codelet_dma(int N, const MapGeom& g, float* out, hipStream_t st);
 int dispatch_codelet_multi(int HP, int pad, const MultiGeom& mg, hipStream_t st);
 int dispatch_lane(int n, const MultiGeom& mg, hipStream_t st);
 int dispatch_codelet_mixed(const MixedGeom& mg, hipStream_t st);
+
+// ---- direct.hip: the cosine-matrix kernel, any (H, W) <= DCTS_MAX_EDGE, energies or coefficients -------------------------
+// its workspace: [basis table of HP][basis table of WP][one HP x WP intermediate tile per workgroup of the grid]
+struct DirectWs {
+  size_t off_ch, off_cw, off_t, total;
+  int grid;
+};
+DirectWs direct_ws(long long nmaps, int HP, int WP);
+// both tables; the status of the two launches (api.hip's memo remembers tables only after a success)
+int launch_basis(float* CHt, int HP, float* CWt, int WP, hipStream_t st);
+int dispatch_direct(int store, int pad, const MapGeom& g, int grid, const float* CHt, const float* CWt, float* T, float* out,
+                    hipStream_t st);
+
+// ---- reduce.hip: what follows the energies (batch sum, running mean), the weighted reduction, the calibration read -------
+int launch_batch_sum(const float* e, long long N, long long C, float* out_c, hipStream_t st);
+int launch_running_mean(const float* e, long long N, long long C, float* fr, float total, hipStream_t st);
+// n <= kMultiMax hook points in one launch; cmax: the largest C_count among them
+constexpr int kMultiMax = 64;
+int launch_running_mean_multi(const dcts_update_desc* descs, int n, long long cmax, hipStream_t st);
+// out[m] = sum_i weights[i] * coeff[m][i]^2 over `nmaps` dense tiles of `hw` coefficients
+int launch_weighted_reduce(const float* coeff, const float* weights, long long nmaps, int hw, float* out, hipStream_t st);
+int launch_stream_read(const float* x, long long n, float* sink, hipStream_t st);
 
 // ---- band.hip: K weighted energies per map (dcts_band_energy_f32) ------------------------------------------------
 int band_kb(int K);                                // K rounded up to 1, 2, 4, 8: the fused kernel's accumulator count

@@ -46,12 +46,12 @@ inline RectGroup rect_group(int HP, int WP, bool store_coeff) {
   return r;
 }
 
-// band.hip, k_band_reduce and api.hip, k_weighted_energy: one wave per map, workgroups of kReduceWaves waves
+// band.hip, k_band_reduce, entropy.hip, k_entropy_reduce and reduce.hip, k_weighted_energy: one wave per map, workgroups of kReduceWaves waves
 constexpr int kReduceWaves = 4;
 constexpr int kReduceMaxBlocks = 4096;
 
-// api.hip, the band fallback: bytes of coefficients per chunk that dcts_band_workspace_bytes sizes the workspace for
-// (one k_band_reduce launch per chunk)
+// api.hip, coeff_layout_bytes(): bytes of coefficients per chunk that dcts_band_workspace_bytes and
+// dcts_entropy_workspace_bytes size the workspace for (one reduction launch per chunk)
 constexpr long long band_chunk_bytes(int HP, int WP) { return (HP <= 65 && WP <= 65) ? (16LL << 20) : (128LL << 20); }
 
 // half.hip, k_upcast_half: one thread per element and step, workgroups of kUpcastThreads threads; api.hip, the staged

@@ -135,7 +135,7 @@ REDUCE_WAVES, REDUCE_MAX_BLOCKS = 4, 4096  # grid_caps.h: kReduceWaves, kReduceM
 
 
 def reduce(cus=None):
-    """band.hip launch_band_reduce and api.hip k_weighted_energy: 4096 workgroups of four waves, one wave per map."""
+    """band.hip launch_band_reduce and reduce.hip launch_weighted_reduce: 4096 workgroups of four waves, one wave per map."""
     return Capacity(REDUCE_MAX_BLOCKS * REDUCE_WAVES, 1)
 
 
@@ -145,7 +145,7 @@ def band_chunk_bytes(hp, wp):
 
 
 def band_fallback_chunk_maps(h, w):
-    """A LOWER bound on api.hip band_fallback_chunk (maps per k_band_reduce launch) with the workspace of
+    """A LOWER bound on api.hip coeff_layout().chunk (maps per k_band_reduce launch) with the workspace of
     dcts_band_workspace_bytes: that is sized for the tile with the odd pad, (H + 1) x (W + 1), so a call without the pad
     gets at least this many maps per chunk."""
     return band_chunk_bytes(h + 1, w + 1) // ((h + 1) * (w + 1) * 4)

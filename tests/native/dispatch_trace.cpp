@@ -5,17 +5,20 @@
 // ordinary kernel objects (they supply the real has_tile2g, has_rect, split_ws, band_table_bytes, codelet_group_size)
 // and this driver. A recorder appends its own name and arguments to the current line and returns 0; the driver prints
 // one line per ABI call: the call, what it dispatched, its return code. Pointers are printed as offsets from four fake
-// bases that are never dereferenced. A call that reaches a launch of api.hip's own kernels (the direct path, the
-// weighted reduction) ends in a positive hipError_t, printed as "launch": the process refuses to start unless the GPU
-// is hidden (HIP_VISIBLE_DEVICES and ROCR_VISIBLE_DEVICES empty, no device counted), so it can never launch on a fake pointer.
+// bases that are never dereferenced. api.hip holds no kernel, so every launch of a call is on record; a positive hipError_t
+// (only the api.hip of a commit that still launched kernels of its own returns one) is printed as "launch". The process
+// refuses to start unless the GPU is hidden (HIP_VISIBLE_DEVICES and ROCR_VISIBLE_DEVICES empty, no device counted), so it
+// can never launch on a fake pointer.
 //
 // Output: the AUTO part first (between "# AUTO begin" and "# AUTO end": what tests/golden/dispatch_trace_auto.txt
-// pins), then the full sweep over explicit families, layouts, workspaces and doubly-bad calls.
+// pins), then the full sweep over explicit families, layouts, workspaces and doubly-bad calls, then the same for the
+// entropy, fp16 / bf16 and channels-last entry points, the basis-table memo, and the reductions.
 #include <cinttypes>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <iterator>
 #include <set>
 #include <string>
 #include <vector>
@@ -64,6 +67,14 @@ void put_geom(const dctsi::MapGeom& g) {
       g.c_count, g.c_begin, g.H, g.W, g.contiguous ? "cont" : "strided");
 }
 
+void put_geom(const dctsi::HalfGeom& g) {
+  put("{%s n%lld sN%lld sC%lld c%d@%d %s}", ptr(g.x).c_str(), g.nmaps, g.strideN, g.strideC, g.c_count, g.c_begin,
+      g.contiguous ? "cont" : "strided");
+}
+void put_geom(const dctsi::NhwcGeom& g) {
+  put("{%s N%lld sN%lld sH%lld sW%lld c%d@%d}", ptr(g.x).c_str(), g.N, g.strideN, g.strideH, g.strideW, g.c_count, g.c_begin);
+}
+
 bool same_item(const dctsi::MultiItem& a, const dctsi::MultiItem& b) {
   return a.g.x == b.g.x && a.g.nmaps == b.g.nmaps && a.g.strideN == b.g.strideN && a.g.strideC == b.g.strideC &&
          a.g.strideH == b.g.strideH && a.g.c_count == b.g.c_count && a.g.c_begin == b.g.c_begin && a.g.H == b.g.H &&
@@ -110,58 +121,129 @@ void put_batch(const dctsi::TileBatch& tb) {
 // ---- the recorders: same signatures as the dispatchers of dcts_internal.h / rect.h -----------------------------------
 namespace dctsi {
 
+// What a recorder returns: 0, the call goes on. A call whose record outgrows kLineCap is stopped with kCut, printed as "cut":
+// dcts_weighted_energy_f32 leaves the 2^40-map limit to its inner calls, each of one sample, so with 2^39 samples it would
+// go on for 2^39 chunks.
+constexpr size_t kLineCap = size_t(1) << 20;
+constexpr int kCut = 1 << 20;
+int more() { return g_line.size() > kLineCap ? kCut : 0; }
+
 int trace_dispatch_codelet(int store, int HP, int WP, int pad, const MapGeom& g, float* out, hipStream_t) {
   put(" codelet st%d %dx%d p%d ", store, HP, WP, pad);
   put_geom(g);
   put(">%s;", ptr(out).c_str());
-  return 0;
+  return more();
 }
 int trace_dispatch_codelet_dma(int N, const MapGeom& g, float* out, hipStream_t) {
   put(" codelet_dma %d ", N);
   put_geom(g);
   put(">%s;", ptr(out).c_str());
-  return 0;
+  return more();
 }
 int trace_dispatch_codelet_multi(int HP, int pad, const MultiGeom& mg, hipStream_t) {
   put(" codelet_multi %d p%d", HP, pad);
   put_items(mg.it, kMultiItems, mg.count, mg.total_groups);
   put(";");
-  return 0;
+  return more();
 }
 int trace_dispatch_lane(int n, const MultiGeom& mg, hipStream_t) {
   put(" lane %d", n);
   put_items(mg.it, kMultiItems, mg.count, mg.total_groups);
   put(";");
-  return 0;
+  return more();
 }
 int trace_dispatch_codelet_mixed(const MixedGeom& mg, hipStream_t) {
   put(" codelet_mixed");
   put_items(mg.it, kMixedItems, mg.count, mg.total_groups);
   put(";");
-  return 0;
+  return more();
 }
 int trace_dispatch_band(int HP, int pad, const MapGeom& g, const float* weights, int K, float* table, float* out, hipStream_t) {
   put(" band %d p%d ", HP, pad);
   put_geom(g);
   put(" w%s K%d t%s >%s;", ptr(weights).c_str(), K, ptr(table).c_str(), ptr(out).c_str());
-  return 0;
+  return more();
 }
 int trace_launch_band_reduce(const float* coeff, const float* weights, long long nmaps, int hw, int K, float* out, hipStream_t) {
   put(" band_reduce %s w%s n%lld hw%d K%d >%s;", ptr(coeff).c_str(), ptr(weights).c_str(), nmaps, hw, K, ptr(out).c_str());
-  return 0;
+  return more();
+}
+int trace_dispatch_entropy(int HP, int pad, const MapGeom& g, float* out, hipStream_t) {
+  put(" entropy %d p%d ", HP, pad);
+  put_geom(g);
+  put(">%s;", ptr(out).c_str());
+  return more();
+}
+int trace_launch_entropy_reduce(const float* coeff, long long nmaps, int hw, float* out, hipStream_t) {
+  put(" entropy_reduce %s n%lld hw%d >%s;", ptr(coeff).c_str(), nmaps, hw, ptr(out).c_str());
+  return more();
+}
+int trace_dispatch_half(int N, int dtype, const HalfGeom& g, float* out, hipStream_t) {
+  put(" half %d d%d ", N, dtype);
+  put_geom(g);
+  put(">%s;", ptr(out).c_str());
+  return more();
+}
+int trace_launch_upcast_half(int dtype, const HalfGeom& g, int H, int W, long long strideH, float* dst, hipStream_t) {
+  put(" upcast d%d ", dtype);
+  put_geom(g);
+  put(" %dx%d sH%lld >%s;", H, W, strideH, ptr(dst).c_str());
+  return more();
+}
+int trace_dispatch_nhwc(int N, int dtype, const NhwcGeom& g, float* out, hipStream_t) {
+  put(" nhwc %d d%d ", N, dtype);
+  put_geom(g);
+  put(">%s;", ptr(out).c_str());
+  return more();
+}
+// direct.hip. Kept short, the record lands on most lines: what of x the call reads, the tile, pad, store flag, grid, the three
+// workspace regions, whether this call built the tables (a launch_basis went before) or reused what the memo knew of
+bool g_tables_built = false;
+int trace_launch_basis(float*, int, float*, int, hipStream_t) {
+  g_tables_built = true;
+  return more();
+}
+int trace_dispatch_direct(int store, int pad, const MapGeom& g, int grid, const float* CHt, const float* CWt, float* T, float* out,
+                          hipStream_t) {
+  put(" direct st%d %dx%d p%d {%s n%lld c%d@%d} g%d %s,%s,%s %s >%s;", store, g.H + pad, g.W + pad, pad, ptr(g.x).c_str(), g.nmaps,
+      g.c_count, g.c_begin, grid, ptr(CHt).c_str(), ptr(CWt).c_str(), ptr(T).c_str(), g_tables_built ? "built" : "reused",
+      ptr(out).c_str());
+  g_tables_built = false;
+  return more();
+}
+// reduce.hip
+int trace_launch_weighted_reduce(const float* coeff, const float* weights, long long nmaps, int hw, float* out, hipStream_t) {
+  put(" weighted_reduce %s w%s n%lld hw%d >%s;", ptr(coeff).c_str(), ptr(weights).c_str(), nmaps, hw, ptr(out).c_str());
+  return more();
+}
+int trace_launch_batch_sum(const float* e, long long N, long long C, float* out_c, hipStream_t) {
+  put(" batch_sum %s N%lld C%lld >%s;", ptr(e).c_str(), N, C, ptr(out_c).c_str());
+  return more();
+}
+int trace_launch_running_mean(const float* e, long long N, long long C, float* fr, float total, hipStream_t) {
+  put(" running_mean %s N%lld C%lld %s t%g;", ptr(e).c_str(), N, C, ptr(fr).c_str(), total);
+  return more();
+}
+int trace_launch_running_mean_multi(const dcts_update_desc* d, int n, long long cmax, hipStream_t) {
+  put(" running_mean_multi n%d cmax%lld %s..%s;", n, cmax, ptr(d[0].energy_nc).c_str(), ptr(d[n - 1].energy_nc).c_str());
+  return more();
+}
+int trace_launch_stream_read(const float* x, long long n, float* sink, hipStream_t) {
+  put(" stream_read %s n%lld >%s;", ptr(x).c_str(), n, ptr(sink).c_str());
+  return more();
 }
 int trace_dispatch_split(int N, const MapGeom& g, float* out, void* workspace, hipStream_t) {
   put(" split %d ", N);
   put_geom(g);
   put(">%s %s;", ptr(out).c_str(), ptr(workspace).c_str());
-  return 0;
+  return more();
 }
 #define TRACE_TILE(NAME)                                                      \
   int trace_dispatch_##NAME(int N, const TileBatch& tb, hipStream_t) {        \
     put(" " #NAME " %d", N);                                                  \
     put_batch(tb);                                                            \
     put(";");                                                                 \
-    return 0;                                                                 \
+    return more();                                                                 \
   }
 TRACE_TILE(fused)
 TRACE_TILE(fused2)
@@ -175,7 +257,7 @@ TRACE_TILE(tile2g_pad)
                             hipStream_t) {                                                                            \
     put(" " #NAME " %d %s n%lld >%s scr%s*%lld;", N, ptr(x).c_str(), nmaps, ptr(out).c_str(), ptr(scratch).c_str(),   \
         scratch_maps);                                                                                                \
-    return 0;                                                                                                         \
+    return more();                                                                                                         \
   }
 TRACE_COEFF(fused_coeff)
 TRACE_COEFF(fused2_coeff)
@@ -187,7 +269,7 @@ int trace_dispatch_rect(const RectGeom& g, float* out, int store_coeff, hipStrea
   put(" rect st%d {%s n%lld sN%lld sC%lld sH%lld c%d@%d %dx%d>%dx%d p%d %s%s}>%s;", store_coeff, ptr(g.x).c_str(), g.nmaps,
       g.strideN, g.strideC, g.strideH, g.c_count, g.c_begin, g.H, g.W, g.HP, g.WP, g.pad, g.contiguous ? "cont" : "strided",
       rest0 ? "" : " REST!=0", ptr(out).c_str());
-  return 0;
+  return more();
 }
 
 }  // namespace dctsi
@@ -196,7 +278,8 @@ namespace {
 
 std::string rc_text(int rc) {
   static const char* const names[] = {"ok", "E_NULL", "E_SHAPE", "E_CHANNELS", "E_STRIDE", "E_WORKSPACE", "E_UNSUPPORTED", "E_ALIGN"};
-  if (rc > 0) return "launch";  // api.hip's own kernels: a launch was attempted (no device here)
+  if (rc == dctsi::kCut) return "cut";
+  if (rc > 0) return "launch";  // an api.hip that launched kernels of its own (no device here)
   if (rc >= -7) return names[-rc];
   return std::to_string(rc);
 }
@@ -206,9 +289,9 @@ void finish(int rc) {
   g_line.clear();
 }
 
-enum Entry { ENERGY, COEFF, WEIGHTED, BAND };
+enum Entry { ENERGY, COEFF, WEIGHTED, BAND, ENTROPY, TYPED, NHWC };
 enum Layout { DENSE, UNALIGNED, PITCHED, BATCH_GAP, SLICE, SLICE_UNALIGNED };
-const char* const kEntryName[] = {"e", "c", "w", "b"};
+const char* const kEntryName[] = {"e", "c", "w", "b", "s", "t", "n"};
 const char* const kLayoutName[] = {"a", "u", "p", "g", "s", "su"};
 
 // one single-tensor call, described by what the sweeps vary
@@ -225,29 +308,47 @@ struct Call {
   const float* weights = WT;
   int64_t strideW = 1;
   int32_t c_begin = -1, c_count = -1;  // -1: from the layout
+  // TYPED and NHWC: the element type; the layouts then count in elements of it
+  int32_t dtype = DCTS_DTYPE_F16;
+  int64_t sW_delta = 0, sH_delta = 0;  // NHWC: added to strideW = C_total and to strideH = W * strideW
 };
 
 int issue(const Call& c, const char* tag) {
   int64_t sH = c.W, C_total = c.C;
   int32_t cb = 0, cc = (int32_t)c.C;
-  const float* x = c.x;
+  const bool typed = c.entry == TYPED || c.entry == NHWC;
+  const size_t elem = typed && c.dtype != DCTS_DTYPE_F32 ? 2 : 4;
+  const char* xb = reinterpret_cast<const char*>(c.x);
   if (c.layout == PITCHED) sH = c.W + 4;
   int64_t sC = c.H * sH, sN = c.C * sC;
-  if (c.layout == UNALIGNED && x) x += 1;
+  if (c.layout == UNALIGNED && xb) xb += elem;
   if (c.layout == BATCH_GAP) sN += 16;
   if (c.layout == SLICE || c.layout == SLICE_UNALIGNED) {
     C_total = c.C + 2;
     cb = 1;
     sN = C_total * sC;
-    if (c.layout == SLICE_UNALIGNED && x) x += 1;
+    if (c.layout == SLICE_UNALIGNED && xb) xb += elem;
   }
   if (c.c_begin != -1) cb = c.c_begin;
   if (c.c_count != -1) cc = c.c_count;
+  const float* x = reinterpret_cast<const float*>(xb);
   put("%s%s %" PRId64 "x%" PRId64 " p%d a%d %s", kEntryName[c.entry], tag, c.H, c.W, c.pad, c.algo, kLayoutName[c.layout]);
   if (c.entry == BAND) put(" K%d", c.K);
+  if (typed) put(" d%d", c.dtype);
   put(" :");
   void* ws = const_cast<void*>(c.ws);
+  if (c.entry == NHWC) {
+    // channels-last: the channel stride is 1, pixels C_total (+ delta) apart; PITCHED pads the rows, BATCH_GAP the samples
+    const int64_t sW = (c.strideW != 1 ? c.strideW : C_total) + c.sW_delta;
+    const int64_t nsH = c.W * sW + c.sH_delta + (c.layout == PITCHED ? 4 * sW : 0);
+    const int64_t nsN = c.H * nsH + (c.layout == BATCH_GAP ? 16 : 0);
+    return dcts_energy_nhwc(xb, c.dtype, c.N, C_total, c.H, c.W, nsN, nsH, sW, cb, cc, c.out, ws, c.ws_bytes, nullptr);
+  }
   switch (c.entry) {
+    case ENTROPY:
+      return dcts_spectral_entropy_f32(x, c.N, C_total, c.H, c.W, sN, sC, sH, c.strideW, cb, cc, c.pad, c.out, ws, c.ws_bytes, nullptr, c.algo);
+    case TYPED:
+      return dcts_energy_typed(xb, c.dtype, c.N, C_total, c.H, c.W, sN, sC, sH, c.strideW, cb, cc, c.pad, c.out, ws, c.ws_bytes, nullptr);
     case ENERGY:
       return dcts_energy_f32_ex(x, c.N, C_total, c.H, c.W, sN, sC, sH, c.strideW, cb, cc, c.pad, c.out, ws, c.ws_bytes, nullptr, c.algo);
     case COEFF:
@@ -285,7 +386,7 @@ std::vector<int> sweep_edges() {
 // ---- multi / mixed lists --------------------------------------------------------------------------------------------
 // What a list holds. BATCHABLE: 16-byte base, base + 1 float, a channel slice of one sample - in turn; all dense, so the
 // large-tile families batch them. WITH_GAP: the same with a gap between the samples of the LAST tensor: it takes a call
-// of its own, which for some shapes ends in a launch - after everything before it has been recorded.
+// of its own (split or direct for some shapes), in the middle of the batch that is still open.
 enum Mix { DENSE_ONLY, BATCHABLE, WITH_GAP };
 const char* const kMixName[] = {"dense", "batchable", "gap-last"};
 dcts_tensor_item make_item(int i, int count, int64_t H, int64_t W, Mix mix) {
@@ -370,7 +471,7 @@ void auto_part(const std::vector<int>& edges) {
                          Shape{224, 224, 0}, Shape{288, 288, 0}, Shape{100, 100, 0}, Shape{67, 67, 0}, Shape{13, 17, 0}})
     for (int count : {2, 3}) trace_multi(count, s.H, s.W, s.pad, BATCHABLE, true);
   for (int e : {72, 96, 8}) trace_multi(33, e, e, 0, BATCHABLE, true);  // across the 32-item chunk; at 96 a 4-byte base joins the fused batch
-  // (a tensor that ends in a launch returns before the open batch is flushed: only a FULL batch before it is on record)
+  // (a tensor that takes a call of its own is served before the open batch is flushed)
   trace_multi(33, 128, 128, 0, WITH_GAP, true);
   trace_multi(33, 71, 71, 1, WITH_GAP, true);
   trace_mixed(12, WITH_GAP, true);
@@ -629,6 +730,233 @@ void size_queries(const std::vector<int>& edges) {
                   dcts_band_workspace_bytes(n, 5, e, e, 8), dcts_has_codelet(e, e), dcts_has_band_kernel(e, e));
 }
 
+// ---- the entry points that came after the first trace: entropy, fp16 / bf16, channels-last ---------------------------
+// (all of it after the sections above, which stay as they were)
+void entropy_sweep() {
+  std::printf("# entropy: fused and fallback shapes, workspaces from none to ample\n");
+  const Shape shapes[] = {{8, 8, 0}, {56, 56, 0}, {9, 9, 1}, {13, 13, 0}, {13, 13, 1}, {23, 23, 1}, {67, 67, 0}, {72, 72, 0}, {71, 71, 1},
+                          {100, 100, 0}, {128, 128, 0}, {224, 224, 0}, {288, 288, 0}, {13, 17, 0}, {512, 512, 0}};
+  for (const Shape& s : shapes)
+    for (Layout l : {DENSE, UNALIGNED, PITCHED, BATCH_GAP, SLICE}) {
+      const size_t tile = (size_t)(s.H + 1) * (s.W + 1) * 4;
+      for (int algo : {DCTS_ALGO_AUTO, DCTS_ALGO_CODELET, DCTS_ALGO_DIRECT})
+        for (int k : {-1, 1, 3, 5, 7, 9, 16, 64, 0}) {
+          Call c;
+          c.entry = ENTROPY;
+          c.H = s.H;
+          c.W = s.W;
+          c.pad = s.pad;
+          c.layout = l;
+          c.algo = algo;
+          c.ws_bytes = k > 0 ? k * tile : k == 0 ? dcts_entropy_workspace_bytes(c.N, c.C, s.H, s.W) : 0;
+          if (k < 0) c.ws = nullptr;
+          char tag[32];
+          std::snprintf(tag, sizeof tag, k > 0 ? "/ws%dt" : k == 0 ? "/wsq" : "/nows", k);
+          trace(c, tag);
+        }
+    }
+  // more samples than a chunk holds, and more channels than a chunk holds
+  for (int e : {13, 72, 100})
+    for (int64_t N : {1, 5})
+      for (int64_t C : {1, 7})
+        for (Layout l : {DENSE, BATCH_GAP}) {
+          Call c;
+          c.entry = ENTROPY;
+          c.H = c.W = e;
+          c.N = N;
+          c.C = C;
+          c.layout = l;
+          c.ws_bytes = 40 * (size_t)(e + 1) * (e + 1) * 4;
+          trace(c, "/nc");
+        }
+}
+
+void typed_sweep() {
+  std::printf("# typed: native and staged shapes, dtypes 0 / 1 / 2 and an invalid one, workspaces from none to ample\n");
+  const Shape shapes[] = {{8, 8, 0}, {56, 56, 0}, {7, 7, 1}, {13, 13, 0}, {13, 13, 1}, {72, 72, 0}, {100, 100, 0}, {288, 288, 0}, {13, 17, 0}};
+  for (const Shape& s : shapes)
+    for (int32_t dtype : {0, 1, 2, 7})
+      for (Layout l : {DENSE, UNALIGNED, PITCHED, BATCH_GAP, SLICE}) {
+        const size_t map = (size_t)s.H * s.W * 4;
+        for (int k : {-1, -2, 0, 1, 3, 7, -3, -4}) {  // maps of stage beyond the fp32 path's own need
+          Call c;
+          c.entry = TYPED;
+          c.dtype = dtype;
+          c.H = s.H;
+          c.W = s.W;
+          c.pad = s.pad;
+          c.layout = l;
+          const size_t inner = dctsi::align_up(dcts_workspace_bytes(c.N, c.C, s.H, s.W), 256);
+          if (k >= 0) c.ws_bytes = inner + k * map;
+          if (k == -1) c.ws = nullptr, c.ws_bytes = 0;
+          if (k == -2) c.ws_bytes = 64;
+          if (k == -3) c.ws_bytes = dcts_typed_workspace_bytes(dtype, c.N, c.C, s.H, s.W + 1);  // (H, W + 1): never native
+          char tag[32];
+          std::snprintf(tag, sizeof tag, k >= 0 ? "/ws+%dm" : k == -1 ? "/nows" : k == -2 ? "/ws64" : k == -3 ? "/wsq" : "/ample", k);
+          trace(c, tag);
+        }
+      }
+  // both chunk regimes: whole samples per chunk, and runs of channels of one sample
+  for (int e : {13, 72, 100})
+    for (int64_t N : {1, 5})
+      for (int64_t C : {1, 7})
+        for (int k : {3, 16})
+          for (Layout l : {DENSE, SLICE}) {
+            Call c;
+            c.entry = TYPED;
+            c.dtype = DCTS_DTYPE_BF16;
+            c.H = c.W = e;
+            c.N = N;
+            c.C = C;
+            c.layout = l;
+            c.ws_bytes = dctsi::align_up(dcts_workspace_bytes(N, C, e, e), 256) + k * (size_t)e * e * 4;
+            trace(c, k == 3 ? "/nc3" : "/nc16");
+          }
+}
+
+void nhwc_sweep() {
+  std::printf("# channels-last: edges with and without a kernel, the three dtypes and an invalid one, the stride rule, a channel slice\n");
+  for (const Shape& s : {Shape{1, 1, 0}, Shape{2, 2, 0}, Shape{4, 4, 0}, Shape{7, 7, 0}, Shape{8, 8, 0}, Shape{9, 9, 0}, Shape{13, 13, 0}, Shape{14, 14, 0},
+                         Shape{16, 16, 0}, Shape{28, 28, 0}, Shape{32, 32, 0}, Shape{56, 56, 0}, Shape{64, 64, 0}, Shape{72, 72, 0}, Shape{8, 4, 0},
+                         Shape{513, 513, 0}})
+    for (int32_t dtype : {0, 1, 2, 7})
+      for (Layout l : {DENSE, UNALIGNED, PITCHED, BATCH_GAP, SLICE}) {
+        Call c;
+        c.entry = NHWC;
+        c.dtype = dtype;
+        c.H = s.H;
+        c.W = s.W;
+        c.layout = l;
+        trace(c);
+      }
+  // strideW >= C_total and strideH >= W * strideW, one element either side
+  for (int e : {8, 28, 9})
+    for (Layout l : {DENSE, SLICE})
+      for (int64_t dW : {-1, 0, 1, 5})
+        for (int64_t dH : {-1, 0, 1}) {
+          Call c;
+          c.entry = NHWC;
+          c.dtype = DCTS_DTYPE_F32;
+          c.H = c.W = e;
+          c.layout = l;
+          c.sW_delta = dW;
+          c.sH_delta = dH;
+          char tag[32];
+          std::snprintf(tag, sizeof tag, "/sW%+d/sH%+d", (int)dW, (int)dH);
+          trace(c, tag);
+        }
+}
+
+const Fault kTypedFaults[] = {
+    {"xodd", [](Call& c) { c.x = reinterpret_cast<const float*>(kX + 1); }},
+    {"dt", [](Call& c) { c.dtype = 7; }},
+};
+
+void doubly_bad_typed() {
+  std::printf("# doubly-bad calls, entropy / typed / channels-last\n");
+  std::vector<Fault> faults(kFaults, kFaults + kNFaults);
+  faults.insert(faults.end(), std::begin(kTypedFaults), std::end(kTypedFaults));
+  const int n = (int)faults.size();
+  for (Entry en : {ENTROPY, TYPED, NHWC})
+    for (int e : {8, 23, 72, 100})
+      for (int v = 0; v < 4; ++v)  // entropy: the algo; typed, channels-last: the dtype
+        for (int i = 0; i < n; ++i)
+          for (int j = i; j < n; ++j) {
+            if (en != ENTROPY && v == 3) continue;
+            Call c;
+            c.entry = en;
+            c.H = c.W = e;
+            if (en == ENTROPY) c.algo = (const int[]){DCTS_ALGO_AUTO, DCTS_ALGO_CODELET, DCTS_ALGO_SPLIT, DCTS_ALGO_FUSED}[v];
+            else c.dtype = v;
+            faults[i].apply(c);
+            if (j != i) faults[j].apply(c);
+            char tag[48];
+            std::snprintf(tag, sizeof tag, "/%s+%s", faults[i].name, faults[j].name);
+            trace(c, tag);
+          }
+}
+
+// ---- the basis-table memo: built once per (workspace, stream, shape), forgotten by whatever writes over the tables -----
+void memo_pairs() {
+  std::printf("# memo: the direct kernel's tables are reused by an identical call and forgotten after a call that overwrites them\n");
+  auto direct = [](int e, const char* tag) {
+    Call c;
+    c.H = c.W = e;
+    c.algo = DCTS_ALGO_DIRECT;
+    trace(c, tag);
+  };
+  auto other = [](Entry en, int e, const char* tag) {
+    Call c;
+    c.entry = en;
+    c.H = c.W = e;
+    c.algo = en == BAND || en == ENTROPY ? DCTS_ALGO_DIRECT : DCTS_ALGO_AUTO;
+    trace(c, tag);
+  };
+  dcts_workspace_invalidate(WS);
+  direct(13, "/first");
+  direct(13, "/again");
+  other(WEIGHTED, 13, "/over");
+  direct(13, "/after-weighted");
+  direct(13, "/again");
+  direct(15, "/other-shape");
+  direct(13, "/after-other-shape");
+  other(BAND, 13, "/over");
+  direct(13, "/after-band");
+  other(ENTROPY, 13, "/over");
+  direct(13, "/after-entropy");
+  other(COEFF, 72, "/over");  // leaf tiles of the large-tile coefficient path
+  direct(13, "/after-coeff");
+  other(TYPED, 13, "/staged");  // the staged route calls run() as dcts_energy_f32 does: same tables, same memo
+  direct(13, "/after-typed");
+  dcts_workspace_invalidate(WS);
+  direct(13, "/after-invalidate");
+  dcts_workspace_invalidate_range(WS + 64, 16);
+  direct(13, "/after-invalidate-range");
+}
+
+// ---- what follows the energies: batch sum, running mean (one hook point, many across the 64-item chunking), the read ----
+void reductions() {
+  std::printf("# reductions\n");
+  put("batch_sum :");
+  finish(dcts_batch_sum_f32(X, 5, 70, OUT, nullptr));
+  put("batch_sum/N0 :");
+  finish(dcts_batch_sum_f32(X, 0, 70, OUT, nullptr));
+  put("batch_sum/out0 :");
+  finish(dcts_batch_sum_f32(X, 5, 70, nullptr, nullptr));
+  put("running_mean :");
+  finish(dcts_running_mean_update_f32(X, 5, 70, OUT, 3.f, nullptr));
+  put("running_mean/C0 :");
+  finish(dcts_running_mean_update_f32(X, 5, 0, OUT, 3.f, nullptr));
+  put("running_mean/x0 :");
+  finish(dcts_running_mean_update_f32(nullptr, 5, 70, OUT, 3.f, nullptr));
+  for (int count : {1, 63, 64, 65, 130})
+    for (int bad : {-1, 0}) {
+      std::vector<dcts_update_desc> d(count);
+      for (int i = 0; i < count; ++i) d[i] = dcts_update_desc{X + 4096 * i, OUT + 512 * i, 4, 16 + i, float(i), 0};
+      if (bad >= 0) d[bad].C_count = 0;
+      put("running_mean_multi %dx bad%d :", count, bad);
+      finish(dcts_running_mean_update_multi_f32(d.data(), count, nullptr));
+    }
+  put("running_mean_multi/null :");
+  finish(dcts_running_mean_update_multi_f32(nullptr, 1, nullptr));
+  put("stream_read :");
+  finish(dcts_debug_stream_read_f32(X, 1 << 20, OUT, nullptr));
+  put("stream_read/n0 :");
+  finish(dcts_debug_stream_read_f32(X, 0, OUT, nullptr));
+}
+
+void size_queries_typed(const std::vector<int>& edges) {
+  std::printf("# size queries, entropy / typed / channels-last\n");
+  for (int e : edges)
+    for (int64_t n : {1, 256})
+      std::printf("sizes2 %d n%" PRId64 " : entropy %zu typed %zu/%zu/%zu/%zu nhwc %zu/%zu has %d/%d/%d\n", e, n,
+                  dcts_entropy_workspace_bytes(n, 5, e, e), dcts_typed_workspace_bytes(0, n, 5, e, e),
+                  dcts_typed_workspace_bytes(1, n, 5, e, e), dcts_typed_workspace_bytes(2, n, 5, e, e),
+                  dcts_typed_workspace_bytes(7, n, 5, e, e), dcts_nhwc_workspace_bytes(0, n, 5, e, e),
+                  dcts_nhwc_workspace_bytes(1, n, 5, e, e), dcts_has_entropy_kernel(e, e), dcts_has_half_kernel(e, e),
+                  dcts_has_nhwc_kernel(e, e));
+}
+
 bool hidden(const char* name) {
   const char* v = std::getenv(name);
   return v && !*v;
@@ -653,5 +981,12 @@ int main() {
   lists();
   doubly_bad();
   size_queries(edges);
+  entropy_sweep();
+  typed_sweep();
+  nhwc_sweep();
+  doubly_bad_typed();
+  memo_pairs();
+  reductions();
+  size_queries_typed(edges);
   return 0;
 }

@@ -76,6 +76,18 @@ int main() {
   EXPECT(dcts_weighted_energy_f32(x, 1, 1, 8, 8, 64, 64, 8, 1, 0, 1, 0, x, out, nullptr, 0, nullptr) == DCTS_E_WORKSPACE);
   EXPECT(dcts_weighted_energy_f32(x, 1, 1, 8, 8, 64, 64, 8, 1, 0, 1, 0, x, out, wsbuf + 4, 1024, nullptr) == DCTS_E_ALIGN);
   EXPECT(dcts_weighted_energy_f32(x, 1, 1, 8, 8, 64, 64, 8, 1, 0, 1, 0, x, out, ws, 8, nullptr) == DCTS_E_WORKSPACE);
+  EXPECT(dcts_spectral_entropy_f32(nullptr, 1, 1, 8, 8, 64, 64, 8, 1, 0, 1, 0, out, ws, sizeof wsbuf, nullptr, DCTS_ALGO_AUTO) == DCTS_E_NULL);
+  EXPECT(dcts_spectral_entropy_f32(x, 1, 1, 13, 13, 169, 169, 13, 1, 0, 1, 0, out, ws, sizeof wsbuf, nullptr, DCTS_ALGO_CODELET) == DCTS_E_UNSUPPORTED);
+  EXPECT(dcts_spectral_entropy_f32(x, 1, 1, 13, 13, 169, 169, 13, 1, 0, 1, 0, out, ws, 64, nullptr, DCTS_ALGO_AUTO) == DCTS_E_WORKSPACE);
+  EXPECT(dcts_energy_typed(x, 7, 1, 1, 8, 8, 64, 64, 8, 1, 0, 1, 0, out, ws, sizeof wsbuf, nullptr) == DCTS_E_UNSUPPORTED);
+  EXPECT(dcts_energy_typed((const char*)x + 1, DCTS_DTYPE_F16, 1, 1, 8, 8, 64, 64, 8, 1, 0, 1, 0, out, ws, sizeof wsbuf, nullptr) == DCTS_E_ALIGN);
+  EXPECT(dcts_energy_typed((const char*)x + 2, DCTS_DTYPE_BF16, 1, 1, 13, 13, 169, 169, 13, 1, 0, 1, 0, out, nullptr, 0, nullptr) == DCTS_E_WORKSPACE);
+  EXPECT(dcts_energy_nhwc(x, 7, 1, 4, 8, 8, 256, 32, 4, 0, 4, out, nullptr, 0, nullptr) == DCTS_E_UNSUPPORTED);
+  EXPECT(dcts_energy_nhwc(x, DCTS_DTYPE_F32, 1, 4, 8, 8, 256, 32, 3, 0, 4, out, nullptr, 0, nullptr) == DCTS_E_STRIDE);
+  EXPECT(dcts_energy_nhwc(x, DCTS_DTYPE_F32, 1, 4, 8, 8, 256, 31, 4, 0, 4, out, nullptr, 0, nullptr) == DCTS_E_STRIDE);
+  EXPECT(dcts_energy_nhwc(x, DCTS_DTYPE_F32, 1, 4, 9, 9, 324, 36, 4, 0, 4, out, nullptr, 0, nullptr) == DCTS_E_UNSUPPORTED);
+  EXPECT(dcts_rank_f32(nullptr, 1, 1, 8, 8, 64, 64, 8, 1, 0, 1, out, nullptr) == DCTS_E_NULL);
+  EXPECT(dcts_rank_f32(x, 1, 1, 65, 65, 4225, 4225, 65, 1, 0, 1, out, nullptr) == DCTS_E_UNSUPPORTED);
   EXPECT(dcts_batch_sum_f32(nullptr, 1, 1, out, nullptr) == DCTS_E_NULL);
   EXPECT(dcts_batch_sum_f32(x, 0, 1, out, nullptr) == DCTS_E_SHAPE);
   EXPECT(dcts_running_mean_update_f32(x, 1, 1, nullptr, 0.f, nullptr) == DCTS_E_NULL);
@@ -159,6 +171,21 @@ int main() {
     EXPECT(rc3 >= 0);
     const int rc4 = dcts_weighted_energy_f32(x, 2, 3, 13, 13, 3 * 169, 169, 13, 1, 0, 3, 0, x, out, ws, sizeof wsbuf, nullptr);
     EXPECT(rc4 >= 0);
+    // the chunked fallbacks: a workspace of a few tiles, so that 2 x 3 maps go in more than one chunk (entropy: whole samples,
+    // then runs of channels; typed: the staged route with one upcast map per chunk)
+    const size_t tile14 = 14 * 14 * 4;
+    for (size_t tiles : {16, 9, 7}) {
+      EXPECT(dcts_spectral_entropy_f32(x, 2, 3, 13, 13, 3 * 169, 169, 13, 1, 0, 3, 0, out, ws, tiles * tile14, nullptr, DCTS_ALGO_AUTO) >= 0);
+      EXPECT(dcts_band_energy_f32(x, 2, 3, 13, 13, 3 * 169, 169, 13, 1, 0, 3, 0, x, 3, out, ws, tiles * tile14, nullptr, DCTS_ALGO_AUTO) >= 0);
+    }
+    const size_t fp32_need = (dcts_workspace_bytes(2, 3, 13, 13) + 255) / 256 * 256;
+    for (size_t maps : {1, 4, 6})
+      EXPECT(dcts_energy_typed(x, DCTS_DTYPE_F16, 2, 3, 13, 13, 3 * 169, 169, 13, 1, 0, 3, 0, out, ws, fp32_need + maps * 169 * 4, nullptr) >= 0);
+    EXPECT(dcts_energy_typed(x, DCTS_DTYPE_BF16, 2, 3, 8, 8, 3 * 64, 64, 8, 1, 0, 3, 0, out, nullptr, 0, nullptr) >= 0);
+    EXPECT(dcts_energy_nhwc(x, DCTS_DTYPE_F16, 2, 8, 8, 8, 512, 64, 8, 1, 6, out, nullptr, 0, nullptr) >= 0);
+    EXPECT(dcts_rank_f32(x, 2, 3, 8, 8, 3 * 64, 64, 8, 1, 0, 3, out, nullptr) >= 0);
+    EXPECT(dcts_weighted_energy_f32(x, 2, 5, 13, 13, 5 * 169, 169, 13, 1, 0, 5, 0, x, out, ws, dcts_workspace_bytes(1, 1, 13, 13) + 4 * 169 * 4,
+                                    nullptr) >= 0);  // two maps per chunk
   }
   std::printf("san_host: %d failures (%d launches succeeded: %s)\n", g_fail, launched, launched ? "a GPU is present" : "no GPU, as expected here");
   return g_fail ? 1 : 0;

@@ -36,3 +36,6 @@ def test_auto_dispatch_matches_golden():
     assert any(l.startswith("e 72x72 p0 a0 a : tile2g 72 ") for l in got)
     assert any(l.startswith("e 224x224 p0 a0 a : tile2d 224 ") for l in got)
     assert any(l.startswith("e 56x56 p0 a0 a : codelet st0 56x56 ") for l in got)
+    assert any(l.startswith("e 67x67 p0 a0 a : direct st0 67x67 p0 ") for l in got)
+    # api.hip launches nothing itself: every call is on record to its end
+    assert not [l for l in got if l.endswith("launch")]

@@ -635,6 +635,46 @@ def test_weighted_calls_of_several_shapes_share_one_workspace_safely():
     assert ops._workspace(dev, stream, 1).data_ptr() == base  # one buffer throughout
 
 
+@pytest.mark.parametrize("n", [13, 72])
+def test_weighted_chunked_by_a_small_workspace_gives_the_same_bits(n):
+    """dcts_weighted_energy_f32 walks every sample in runs of as many channels as its workspace holds coefficient tiles
+    for. A workspace of the inner call's own need plus four tiles holds two maps per chunk: N = 2, C = 5 goes in runs of
+    2, 2, 1 channels per sample (13: the small-tile coefficient kernel inside, 72: tile2g's coefficient path). The result must be, bit
+    for bit, that of the ample workspace, which in turn meets the float64 definition within the weighted test's bound;
+    the output lies NaN-filled between guard words."""
+    from dct_pruning_amd import _lib
+
+    lib = _lib.load()
+    N, C = 2, 5
+    x = synth(N, C, n, n, 11, dead=False)
+    w = torch.rand(n, n, generator=torch.Generator().manual_seed(12))
+    ref = torch.from_numpy(orc.weighted_energy_nc_f64(x, w.numpy()))
+    xd, wd = x.cuda(), w.cuda()
+    stream = torch.cuda.current_stream().cuda_stream
+    guard = 16
+    tile = n * n * 4
+    small = lib.dcts_workspace_bytes(1, 1, n, n) + 4 * tile
+    ample = lib.dcts_weighted_workspace_bytes(N, C, n, n)
+    assert small < ample
+    outs = []
+    for ws_bytes in (ample, small):
+        out = torch.full((N * C + 2 * guard,), float("nan"), device="cuda")
+        out[:guard] = -123.0
+        out[guard + N * C:] = -123.0
+        ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device="cuda")
+        _lib.check(lib.dcts_weighted_energy_f32(xd.data_ptr(), N, C, n, n, xd.stride(0), xd.stride(1), xd.stride(2), 1, 0, C, 0,
+                                                wd.data_ptr(), out[guard:].data_ptr(), ws.data_ptr(), ws_bytes, stream))
+        lib.dcts_workspace_invalidate_range(ws.data_ptr(), ws.numel())
+        torch.cuda.synchronize()
+        assert (out[:guard] == -123.0).all() and (out[guard + N * C:] == -123.0).all()
+        outs.append(out[guard:guard + N * C].view(N, C).cpu())
+    assert not torch.isnan(outs[0]).any()
+    err = rel_err(outs[0], ref)
+    print("WEIGHTED_CHUNKED %dx%d ample err=%.3g" % (n, n, err))
+    assert err <= 2e-5
+    assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32))
+
+
 @pytest.mark.parametrize("n", [72, 256, 288])
 def test_large_tile_with_a_4_byte_aligned_base(n):
     """The two-launch path stages with 16-byte direct-to-LDS loads and refuses a view whose base is only 4-byte aligned. The
