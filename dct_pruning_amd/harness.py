@@ -44,7 +44,13 @@ Additions (opt-in, results identical on fixed batches):
   channels_last=True  the net and every input batch are converted to torch.channels_last; the hooks hand on whatever
                       layout arrives and ops.energy_nc reads channels-last tensors where they lie (dcts_energy_nhwc).
                       Same files. Combines with autocast. The "dct" criterion only, not with deferred=True, not u2netp.
+
+A criterion is defined in one place here: its scorer `_score_<name>(x, c_begin, c_count, pad)` and its row of the
+criterion table below it (output root and file prefix, hook kinds and odd pad, score width, LPT cost, supported modes and
+excluded nets). The hooks, _PointHook, imp_score, check_options and importance_generation.py's parser read the row, so
+adding a criterion takes an operator in ops.py, a scorer, a row, and tests and docs for it.
 """
+import collections
 import contextlib
 import os
 
@@ -61,7 +67,6 @@ _rank_nc = ops.rank_nc
 _band_energy_nc = ops.band_energy_nc
 _entropy_nc = ops.spectral_entropy_nc
 
-CRITERIA = ("dct", "rank", "bands", "entropy")
 AUTOCAST = {"fp16": torch.float16, "bf16": torch.bfloat16}
 
 # the band criterion's partition (K, kind): imp_score(criterion="bands", bands=...) sets it for its hooks
@@ -77,6 +82,54 @@ def _band_weights(H, W, device):
         w = _band_weight_cache[key] = torch.from_numpy(_bands.partition(H, W, *_band_cfg)).to(device)
     return w
 
+
+# The scorers: (x, c_begin, c_count, pad) -> [N, c_count] (bands: [N, c_count, K]) of a channel range of x; pad is the
+# cv2 path's odd front pad. They read the swap points above when they are called.
+def _score_dct(x, c_begin, c_count, pad):
+    return _energy_nc(x, c_begin=c_begin, c_count=c_count, pad_front_if_odd=pad)
+
+
+def _score_rank(x, c_begin, c_count, pad):
+    """HRank's per-map matrix_rank (no odd pad: the rank is taken of the map as it is)."""
+    return _rank_nc(x, c_begin=c_begin, c_count=c_count)
+
+
+def _score_bands(x, c_begin, c_count, pad):
+    H, W = x.shape[2], x.shape[3]
+    p = 1 if (pad and H % 2 == 1) else 0
+    return _band_energy_nc(x, _band_weights(H + p, W + p, x.device), c_begin=c_begin, c_count=c_count, pad_front_if_odd=pad)
+
+
+def _score_entropy(x, c_begin, c_count, pad):
+    return _entropy_nc(x, c_begin=c_begin, c_count=c_count, pad_front_if_odd=pad)
+
+
+# A criterion is its scorer above and its row here; everything below reads the row.
+#   root, prefix  output root under the CWD; the file stem is the schedule's with its leading imp_ replaced by `prefix`
+#                 (a stem without imp_, U2-Net-p's net.<module path>, gets it in front); None keeps the stem
+#   what          the hooks' docstring: what stands in place of get_feature_hook's DCT energy
+#   kinds, pad    the hook kinds it serves, and whether it takes the odd front pad of the "last12" / "input" kinds
+#   banded        scores are [N, c, K] for the K of bands=(K, kind): files hold [C, K], the output dir ends in _<kind><K>
+#   cost          LPT cost of one channel of an H x W hook point: the bytes the DCT kernels stream, or the kernel's arithmetic
+#   deferred, autocast, channels_last   the modes it supports; `excluded`: {net: why it is out of scope}
+Criterion = collections.namedtuple(
+    "Criterion", "name root prefix score what kinds pad banded cost deferred autocast channels_last excluded",
+    defaults=(("full", "last12", "input"), True, False, lambda H, W: H * W, False, False, False, {}))
+_TABLE = {c.name: c for c in (
+    Criterion("dct", "importance_score", None, _score_dct, "the DCT energy of every map",
+              deferred=True, autocast=True, channels_last=True),
+    Criterion("rank", "rank_conv", "rank_", _score_rank,
+              "HRank's score: the numerical rank of every map, c.view(a, -1).float().sum(0), then the running mean of "
+              "utils/common.py:271-277. The ranks are exact small integers in fp32, so the batch sum is exact",
+              kinds=("full", "last12"), pad=False, cost=lambda H, W: H * W * min(H, W),
+              excluded={"u2netp": "supports edges up to 64; u2netp (up to 288) is out of scope"}),
+    Criterion("bands", "band_score", "band_", _score_bands,
+              "the DCT energy split into K bands: the accumulator's view(a, -1).sum(0) runs over the flat [a, C*K] view, "
+              "so feature_result is the [C, K] spectrum in row-major order", banded=True),
+    Criterion("entropy", "entropy_score", "ent_", _score_entropy, "the spectral entropy of every map"),
+)}
+CRITERIA = tuple(_TABLE)
+
 # the reference's module globals (utils/common.py:258-259)
 _acc = HostAccumulator()
 
@@ -85,58 +138,25 @@ def _scored_tensor(kind, inputs, output):
     return inputs[0] if kind == "input" else output
 
 
-def _hook_energy(kind, x):
-    b = x.shape[1]
+def _kind_slice(crit, kind, C):
+    """(c_begin, c_count, pad_front_if_odd) of a hook kind on a C-channel tensor, the rule of the reference's three
+    hooks: "full" is every channel as it is, "last12" the channels [C-12, C) on the cv2 path (odd front pad), "input"
+    every channel on the cv2 path."""
+    if kind not in crit.kinds:
+        raise ValueError("the %s criterion has no %s hook (U2-Net-p is out of its scope)" % (crit.name, kind))
     if kind == "last12":
-        return _energy_nc(x, c_begin=b - 12, c_count=12, pad_front_if_odd=True)
-    if kind == "input":
-        return _energy_nc(x, pad_front_if_odd=True)
-    return _energy_nc(x)
-
-
-def _hook_rank(kind, x):
-    """HRank's per-map matrix_rank over the same channels as the DCT hook of that kind (no odd pad: the rank is
-    taken of the map as it is)."""
-    if kind == "last12":
-        b = x.shape[1]
-        return _rank_nc(x, c_begin=b - 12, c_count=12)
-    if kind == "input":
-        raise ValueError("the rank criterion has no input hook (U2-Net-p is out of its scope)")
-    return _rank_nc(x)
-
-
-def _band_piece(x, c_begin, c_count, pad):
-    """[N, c_count, K] band energies of a channel range of x (pad: the cv2 path's odd front pad)."""
-    H, W = x.shape[2], x.shape[3]
-    p = 1 if (pad and H % 2 == 1) else 0
-    return _band_energy_nc(x, _band_weights(H + p, W + p, x.device), c_begin=c_begin, c_count=c_count,
-                           pad_front_if_odd=bool(pad))
-
-
-def _hook_bands(kind, x):
-    """The K band energies of every map the DCT hook of that kind scores (same channels, same odd pad): [N, c, K]."""
-    b = x.shape[1]
-    if kind == "last12":
-        return _band_piece(x, b - 12, 12, True)
-    return _band_piece(x, 0, b, kind == "input")
-
-
-def _hook_entropy(kind, x):
-    """The spectral entropy of every map the DCT hook of that kind scores (same channels, same odd pad)."""
-    b = x.shape[1]
-    if kind == "last12":
-        return _entropy_nc(x, c_begin=b - 12, c_count=12, pad_front_if_odd=True)
-    if kind == "input":
-        return _entropy_nc(x, pad_front_if_odd=True)
-    return _entropy_nc(x)
+        return C - 12, 12, crit.pad
+    return 0, C, crit.pad and kind == "input"
 
 
 def _hook_score(criterion, kind, x):
-    if criterion == "bands":
-        return _hook_bands(kind, x)
-    if criterion == "entropy":
-        return _hook_entropy(kind, x)
-    return _hook_rank(kind, x) if criterion == "rank" else _hook_energy(kind, x)
+    """The scores of every map the hook of that kind scores."""
+    crit = _TABLE[criterion]
+    return crit.score(x, *_kind_slice(crit, kind, x.shape[1]))
+
+
+def _hook_energy(kind, x):
+    return _hook_score("dct", kind, x)
 
 
 def get_feature_hook(self, input, output):
@@ -170,54 +190,25 @@ def make_weighted_feature_hook(weights_for):
     return hook
 
 
-def get_feature_hook_rank(self, input, output):
-    """HRank's hook: c = [matrix_rank(output[i, j]) for every map]; c.view(a, -1).float().sum(0), then the running
-    mean of utils/common.py:271-277. The ranks are exact small integers in fp32, so the batch sum is exact."""
-    _acc.update(_hook_rank("full", output))
+def _make_hook(crit, kind, like):
+    """The hook `like` (one of the reference's three above) with another criterion's score: <like's name>_<criterion>."""
+    def hook(self, input, output):
+        _acc.update(_hook_score(crit.name, kind, _scored_tensor(kind, input, output)))
+
+    hook.__name__ = hook.__qualname__ = "%s_%s" % (like.__name__, crit.name)
+    hook.__doc__ = "%s with %s." % (like.__name__, crit.what)
+    return hook
 
 
-def get_feature_hook_densenet_rank(self, input, output):
-    """HRank's densenet hook: channels [b-12, b)."""
-    _acc.update(_hook_rank("last12", output))
-
-
-def get_feature_hook_bands(self, input, output):
-    """get_feature_hook with the energy split into K bands: the accumulator's view(a, -1).sum(0) runs over the flat
-    [a, C*K] view, so feature_result is the [C, K] spectrum in row-major order."""
-    _acc.update(_hook_bands("full", output))
-
-
-def get_feature_hook_densenet_bands(self, input, output):
-    """channels [b-12, b), cv2 path (odd front pad)."""
-    _acc.update(_hook_bands("last12", output))
-
-
-def get_feature_hook_u2net_input_bands(self, input, output):
-    """scores input[0], cv2 path (odd front pad)."""
-    _acc.update(_hook_bands("input", input[0]))
-
-
-def get_feature_hook_entropy(self, input, output):
-    """get_feature_hook with the spectral entropy of every map in place of its DCT energy."""
-    _acc.update(_hook_entropy("full", output))
-
-
-def get_feature_hook_densenet_entropy(self, input, output):
-    """channels [b-12, b), cv2 path (odd front pad)."""
-    _acc.update(_hook_entropy("last12", output))
-
-
-def get_feature_hook_u2net_input_entropy(self, input, output):
-    """scores input[0], cv2 path (odd front pad)."""
-    _acc.update(_hook_entropy("input", input[0]))
-
-
-_ENTROPY_HOOKS = {"full": get_feature_hook_entropy, "last12": get_feature_hook_densenet_entropy,
-                  "input": get_feature_hook_u2net_input_entropy}
-_BAND_HOOKS = {"full": get_feature_hook_bands, "last12": get_feature_hook_densenet_bands,
-               "input": get_feature_hook_u2net_input_bands}
-_HOOKS = {"full": get_feature_hook, "last12": get_feature_hook_densenet, "input": get_feature_hook_u2net_input}
-_RANK_HOOKS = {"full": get_feature_hook_rank, "last12": get_feature_hook_densenet_rank}
+# (criterion, kind) -> the module-level hook of the per-hook host mode: get_feature_hook, get_feature_hook_rank,
+# get_feature_hook_densenet_bands, get_feature_hook_u2net_input_entropy, ...
+_HOOKS = {("dct", "full"): get_feature_hook, ("dct", "last12"): get_feature_hook_densenet,
+          ("dct", "input"): get_feature_hook_u2net_input}
+for _crit in _TABLE.values():
+    for _kind in _crit.kinds:
+        if (_crit.name, _kind) not in _HOOKS:
+            _hook = _HOOKS[_crit.name, _kind] = _make_hook(_crit, _kind, _HOOKS["dct", _kind])
+            globals()[_hook.__name__] = _hook
 
 
 def _net_device(net):
@@ -282,14 +273,12 @@ def _done_line(net_name, idx, stem):
 
 
 def _file_stem(criterion, stem):
-    """rank files: the schedule's stem with the leading imp_ replaced by rank_ (imp_conv3 -> rank_conv3)."""
-    if criterion == "rank" and stem.startswith("imp_"):
-        return "rank_" + stem[len("imp_"):]
-    if criterion == "bands":  # imp_conv3 -> band_conv3; U2-Net-p's net.<module path> -> band_net.<module path>
-        return "band_" + (stem[len("imp_"):] if stem.startswith("imp_") else stem)
-    if criterion == "entropy":  # the band files' rule: imp_conv3 -> ent_conv3, net.<module path> -> ent_net.<module path>
-        return "ent_" + (stem[len("imp_"):] if stem.startswith("imp_") else stem)
-    return stem
+    """The schedule's stem under the criterion's prefix: imp_conv3 -> rank_conv3 / band_conv3 / ent_conv3, U2-Net-p's
+    net.<module path> -> band_net.<module path>; "dct" keeps the stem."""
+    prefix = _TABLE[criterion].prefix
+    if prefix is None:
+        return stem
+    return prefix + (stem[len("imp_"):] if stem.startswith("imp_") else stem)
 
 
 def _save(out_dir, net_name, pt, scores, criterion="dct"):
@@ -313,16 +302,14 @@ class _PointHook:
     def __init__(self, kind, accumulate, device, batch=None, key=None, deferred=False, ranges=None, nominal_c=None,
                  criterion="dct"):
         self.kind, self.accumulate, self.device, self.acc = kind, accumulate, device, None
-        self.criterion = criterion
+        self.crit = _TABLE[criterion]
         self.batch, self.key, self.deferred = batch, key, deferred
         self.ranges, self.nominal_c, self.accs = ranges, nominal_c, {}
         self.width = None  # K of the band criterion: scores come back as [c, K]
 
     def _pieces(self, x):
         """(key, c_begin, c_count, pad_front_if_odd) of every operator call this hook makes on x."""
-        b = x.shape[1]
-        base, count = (b - 12, 12) if self.kind == "last12" else (0, b)
-        pad = self.kind != "full"
+        base, count, pad = _kind_slice(self.crit, self.kind, x.shape[1])
         if self.ranges is None:
             return [(self.key, base, count, pad)]
         if count != self.nominal_c:
@@ -334,24 +321,11 @@ class _PointHook:
 
     def __call__(self, module, inputs, output):
         x = _scored_tensor(self.kind, inputs, output)
-        if self.ranges is None and not (self.deferred and self.batch is not None):
-            pieces = [(self.key, None, None, None)]  # the reference's own three calls, argument for argument
-        else:
-            pieces = self._pieces(x)
-        for key, cb, cc, pad in pieces:
+        for key, cb, cc, pad in self._pieces(x):
             if self.deferred and self.batch is not None:
                 self.batch.add_tensor(key, x, cb, cc, pad)
                 continue
-            if cb is None:
-                e = _hook_score(self.criterion, self.kind, x)
-            elif self.criterion == "rank":
-                e = _rank_nc(x, c_begin=cb, c_count=cc)
-            elif self.criterion == "bands":
-                e = _band_piece(x, cb, cc, pad)
-            elif self.criterion == "entropy":
-                e = _entropy_nc(x, c_begin=cb, c_count=cc, pad_front_if_odd=pad)
-            else:
-                e = _energy_nc(x, c_begin=cb, c_count=cc, pad_front_if_odd=pad)
+            e = self.crit.score(x, cb, cc, pad)
             if e.dim() == 3:  # [N, c, K] band energies: the accumulators see the dense [N, c*K] view
                 self.width = e.shape[2]
                 e = e.reshape(e.shape[0], -1)
@@ -391,6 +365,40 @@ class _ChannelsLastLoader:
             yield data.contiguous(memory_format=torch.channels_last), target
 
 
+def check_options(criterion, net, deferred=False, autocast=None, channels_last=False, bands=(4, "square")):
+    """Raises the ValueError of the first rule an imp_score call with these options breaks: what the criterion's row
+    supports, and the two rules that hold for every criterion (autocast and channels_last have no deferred mode,
+    channels_last does not cover u2netp). importance_generation.py's parser rejects its command lines with it."""
+    if criterion not in CRITERIA:
+        raise ValueError("imp_score: unknown criterion %r (expected one of %s)" % (criterion, ", ".join(CRITERIA)))
+    crit = _TABLE[criterion]
+    if autocast is not None:
+        if autocast not in AUTOCAST:
+            raise ValueError("imp_score: autocast must be None, 'fp16' or 'bf16', got %r" % (autocast,))
+        if deferred:
+            raise ValueError("imp_score: autocast has no deferred mode (no multi-tensor half-precision launch); "
+                             "use single_sweep / accumulate instead")
+        if not crit.autocast:
+            raise ValueError("imp_score: autocast supports criterion='dct' only (the %s kernels take float32)" % criterion)
+    if channels_last:
+        if deferred:
+            raise ValueError("imp_score: channels_last has no deferred mode (the multi-tensor launches take NCHW tensors); "
+                             "use single_sweep / accumulate instead")
+        if not crit.channels_last:
+            raise ValueError("imp_score: channels_last supports criterion='dct' only (the %s kernels take NCHW tensors)"
+                             % criterion)
+        if net == "u2netp":
+            raise ValueError("imp_score: channels_last does not cover u2netp (dict batches, and no channels-last "
+                             "kernel for its 288 x 288 maps)")
+    if deferred and not crit.deferred:
+        raise ValueError("imp_score: criterion=%r has no deferred mode; use single_sweep / accumulate instead" % criterion)
+    if net in crit.excluded:
+        raise ValueError("imp_score: criterion=%r %s" % (criterion, crit.excluded[net]))
+    if crit.banded and (not 1 <= int(bands[0]) <= _bands.BAND_MAX or bands[1] not in _bands.KINDS):
+        raise ValueError("imp_score: bands=(K, kind) needs 1 <= K <= %d and kind in %s, got %r"
+                         % (_bands.BAND_MAX, _bands.KINDS, (bands,)))
+
+
 def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host", group=None, deferred=False,
               criterion="dct", bands=(4, "square"), autocast=None, channels_last=False):
     """Counterpart of utils/common.py:367-977. `args` needs .net, .limit (and whatever
@@ -404,48 +412,19 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
     channels_last=True converts the net (in place) and every input batch to torch.channels_last; the tensors the hooks
     then see are scored in the layout they arrive in (criterion "dct" only, not with deferred, not u2netp)."""
     global _acc, _band_cfg
-    if criterion not in CRITERIA:
-        raise ValueError("imp_score: unknown criterion %r (expected one of %s)" % (criterion, ", ".join(CRITERIA)))
-    if autocast is not None:
-        if autocast not in AUTOCAST:
-            raise ValueError("imp_score: autocast must be None, 'fp16' or 'bf16', got %r" % (autocast,))
-        if deferred:
-            raise ValueError("imp_score: autocast has no deferred mode (no multi-tensor half-precision launch); "
-                             "use single_sweep / accumulate instead")
-        if criterion != "dct":
-            raise ValueError("imp_score: autocast supports criterion='dct' only (the %s kernels take float32)" % criterion)
-    if channels_last:
-        if deferred:
-            raise ValueError("imp_score: channels_last has no deferred mode (the multi-tensor launches take NCHW tensors); "
-                             "use single_sweep / accumulate instead")
-        if criterion != "dct":
-            raise ValueError("imp_score: channels_last supports criterion='dct' only (the %s kernels take NCHW tensors)"
-                             % criterion)
-        if args.net == "u2netp":
-            raise ValueError("imp_score: channels_last does not cover u2netp (dict batches, and no channels-last "
-                             "kernel for its 288 x 288 maps)")
-    if criterion == "rank" and deferred:
-        raise ValueError("imp_score: criterion='rank' has no deferred mode; use single_sweep / accumulate instead")
-    if criterion == "rank" and args.net == "u2netp":
-        raise ValueError("imp_score: criterion='rank' supports edges up to 64; u2netp (up to 288) is out of scope")
-    if criterion == "entropy" and deferred:
-        raise ValueError("imp_score: criterion='entropy' has no deferred mode; use single_sweep / accumulate instead")
-    if criterion == "bands":
-        if deferred:
-            raise ValueError("imp_score: criterion='bands' has no deferred mode; use single_sweep / accumulate instead")
-        K, kind = int(bands[0]), bands[1]
-        if not 1 <= K <= _bands.BAND_MAX or kind not in _bands.KINDS:
-            raise ValueError("imp_score: bands=(K, kind) needs 1 <= K <= %d and kind in %s, got %r"
-                             % (_bands.BAND_MAX, _bands.KINDS, (bands,)))
-        _band_cfg = (K, kind)
+    check_options(criterion, args.net, deferred, autocast, channels_last, bands)
+    crit = _TABLE[criterion]
     if not hasattr(args, "limit"):
         # utils/load_models.py:819 calls imp_score from prune_*.py whose parsers define no --limit
         # (AttributeError in the reference as shipped); fall back to importance_generation.py's default
         args.limit = 5
-    root = {"rank": "rank_conv", "bands": "band_score", "entropy": "entropy_score"}.get(criterion, "importance_score")
+    root = crit.root
     out_dir = root + "/" + args.net + "_limit" + str(args.limit)
-    if criterion == "bands":
-        out_dir += "_%s%d" % (_band_cfg[1], _band_cfg[0])
+    width = 1  # floats per channel in a score
+    if crit.banded:
+        _band_cfg = (int(bands[0]), bands[1])
+        width = _band_cfg[0]
+        out_dir += "_%s%d" % (_band_cfg[1], width)
     world, rank = 1, 0
     if group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
         world = torch.distributed.get_world_size(group)
@@ -487,8 +466,8 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
     # cutting it would repeat its forward sweep on another rank.
     scored = [schedules.scored_shape(p) for p in pts]
     chans = [sc[1] for sc in scored]
-    # LPT cost per channel: the bytes the DCT kernels stream, or the rank kernel's O(H W min(H, W)) arithmetic
-    cost_pc = [float(p.H * p.W * min(p.H, p.W)) if criterion == "rank" else float(p.H * p.W) for p in pts]
+    # LPT cost per channel: the bytes the DCT kernels stream, or the rank kernel's O(H W min(H, W)) arithmetic (the row's)
+    cost_pc = [float(crit.cost(p.H, p.W)) for p in pts]
     if world > 1:
         total_cost = sum(c * k for c, k in zip(chans, cost_pc))
         cut = total_cost / (8.0 * world) if single_sweep else None  # G = 8: every net within 6 % of balance
@@ -537,13 +516,12 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
                 handler.remove()
                 results[k] = hook.scores()
             else:
-                table = {"rank": _RANK_HOOKS, "bands": _BAND_HOOKS, "entropy": _ENTROPY_HOOKS}.get(criterion, _HOOKS)
-                handler = layer.register_forward_hook(table[pt.kind])
+                handler = layer.register_forward_hook(_HOOKS[criterion, pt.kind])
                 sweep(net, train_loader, args.limit)
                 handler.remove()
                 results[k] = np.ascontiguousarray(_acc.feature_result.numpy(), dtype=np.float32)
-                if criterion == "bands":
-                    results[k] = results[k].reshape(-1, _band_cfg[0])
+                if crit.banded:
+                    results[k] = results[k].reshape(-1, width)
                 _acc.reset()
             if world == 1:
                 _save(out_dir, args.net, pt, results[k], criterion)
@@ -552,8 +530,7 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
             return
 
     if world > 1:
-        layer_scores = _gather_results(results, units, len(pts), owner, world, rank, dev, group,
-                                       width=_band_cfg[0] if criterion == "bands" else 1)
+        layer_scores = _gather_results(results, units, len(pts), owner, world, rank, dev, group, width=width)
     else:
         layer_scores = {units[k].layer: results[k] for k in mine}
     if rank == 0:

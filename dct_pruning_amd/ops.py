@@ -26,7 +26,7 @@ def _workspace(device, stream_ptr, nbytes):
 _HALF_DTYPES = {torch.float16: 1, torch.bfloat16: 2}
 
 
-def _check_input(x, half_ok=False):
+def _check_input(x, half_ok=False, algo=ALGO_AUTO):
     if not isinstance(x, torch.Tensor):
         raise TypeError("expected a torch.Tensor")
     if x.dim() != 4:
@@ -38,6 +38,8 @@ def _check_input(x, half_ok=False):
         raise RuntimeError(
             "dct_pruning_amd runs on the GPU only: got a %s tensor. There is no CPU fallback; "
             "the CPU restatement under oracle/ is test infrastructure." % x.device)
+    if x.dtype != torch.float32 and algo != ALGO_AUTO:
+        raise ValueError("float16 / bfloat16 feature maps take ALGO_AUTO only, got algo=%r" % (algo,))
 
 
 def _slice(x, c_begin, c_count):
@@ -47,24 +49,50 @@ def _slice(x, c_begin, c_count):
     return int(c_begin), int(c_count)
 
 
+def _rows(x, dense=False):
+    """x with W-contiguous rows, copied if need be; dense: without a row pitch as well (the list entry points)."""
+    W = x.shape[3]
+    if x.stride(3) != 1 or (x.stride(2) != W if dense else x.stride(2) < W):
+        x = x.contiguous()
+    return x
+
+
+def _open(x, c_begin, c_count, out=None, half_ok=False, algo=ALGO_AUTO, rows="pitched"):
+    """The opening every entry point shares: input check, channel slice, the [N, c_count] output (out=None: a new one;
+    a tensor: checked; False: the caller makes its own), the .contiguous() fallback (rows: "pitched", "dense" for the
+    list entry points, None to leave x as it lies) and the current stream of x's device.
+    Returns (x, c_begin, c_count, out, stream)."""
+    _check_input(x, half_ok, algo)
+    c_begin, c_count = _slice(x, c_begin, c_count)
+    N = x.shape[0]
+    if out is None:
+        out = torch.empty((N, c_count), dtype=torch.float32, device=x.device)
+    elif out is not False and (out.shape != (N, c_count) or out.dtype != torch.float32 or not out.is_contiguous()
+                               or out.device != x.device):
+        raise ValueError("out must be a contiguous float32 [N, c_count] tensor on x's device")
+    if rows is not None:
+        x = _rows(x, rows == "dense")
+    return x, c_begin, c_count, out, torch.cuda.current_stream(x.device).cuda_stream
+
+
+def _launch(device, fn, *args):
+    """fn(*args) with `device` current; a status other than 0 raises (_lib.check)."""
+    with torch.cuda.device(device):
+        _lib.check(fn(*args))
+
+
 def has_codelet(H, W):
     return bool(_lib.load().dcts_has_codelet(H, W))
 
 
-def _call(fn_name, x, c_begin, c_count, pad_front_if_odd, out, algo):
+def _call(fn_name, x, c_begin, c_count, pad_front_if_odd, out, algo, stream):
     lib = _lib.load()
     N, C, H, W = x.shape
-    if x.stride(3) != 1 or x.stride(2) < W:
-        x = x.contiguous()
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    nbytes = lib.dcts_workspace_bytes(N, c_count, H, W)
-    ws = _workspace(x.device, stream, nbytes)
-    with torch.cuda.device(x.device):
-        code = getattr(lib, fn_name)(
+    ws = _workspace(x.device, stream, lib.dcts_workspace_bytes(N, c_count, H, W))
+    _launch(x.device, getattr(lib, fn_name),
             x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
             c_begin, c_count, 1 if pad_front_if_odd else 0, out.data_ptr(),
             ws.data_ptr(), ws.numel(), stream, algo)
-    _lib.check(code)
     return out
 
 
@@ -74,23 +102,18 @@ def has_half_kernel(H, W):
     return bool(_lib.load().dcts_has_half_kernel(H, W))
 
 
-def _call_half(x, c_begin, c_count, pad_front_if_odd, out):
+def _call_half(x, c_begin, c_count, pad_front_if_odd, out, stream):
     lib = _lib.load()
     N, C, H, W = x.shape
-    if x.stride(3) != 1 or x.stride(2) < W:
-        x = x.contiguous()
     dtype = _HALF_DTYPES[x.dtype]
-    stream = torch.cuda.current_stream(x.device).cuda_stream
     nbytes = lib.dcts_typed_workspace_bytes(dtype, N, c_count, H, W)
     if lib.dcts_has_half_kernel(H, W) and (x.stride(2) != W or (pad_front_if_odd and H % 2 == 1)):
         # a native shape the kernel does not take is staged like the others: sized as the header says, for (H, W + 1)
         nbytes = lib.dcts_typed_workspace_bytes(dtype, N, c_count, H, W + 1)
     ws = _workspace(x.device, stream, nbytes)
-    with torch.cuda.device(x.device):
-        code = lib.dcts_energy_typed(
+    _launch(x.device, lib.dcts_energy_typed,
             x.data_ptr(), dtype, N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
             c_begin, c_count, 1 if pad_front_if_odd else 0, out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-    _lib.check(code)
     return out
 
 
@@ -124,15 +147,11 @@ def energy_route(shape, stride, pad_front_if_odd=False, algo=ALGO_AUTO, has_kern
 _NHWC_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
-def _call_nhwc(x, c_begin, c_count, out):
-    lib = _lib.load()
+def _call_nhwc(x, c_begin, c_count, out, stream):
     N, C, H, W = x.shape
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    with torch.cuda.device(x.device):
-        code = lib.dcts_energy_nhwc(
+    _launch(x.device, _lib.load().dcts_energy_nhwc,
             x.data_ptr(), _NHWC_DTYPES[x.dtype], N, C, H, W, x.stride(0), x.stride(2), x.stride(3),
             c_begin, c_count, out.data_ptr(), None, 0, stream)
-    _lib.check(code)
     return out
 
 
@@ -148,30 +167,22 @@ def energy_nc(x, c_begin=0, c_count=None, pad_front_if_odd=False, algo=ALGO_AUTO
     tensor whose rows are not W-contiguous is copied with .contiguous() first.
     Enqueues on the current stream of x's device; no synchronisation.
     """
-    _check_input(x, half_ok=True)
-    if x.dtype != torch.float32 and algo != ALGO_AUTO:
-        raise ValueError("float16 / bfloat16 feature maps take ALGO_AUTO only, got algo=%r" % (algo,))
-    c_begin, c_count = _slice(x, c_begin, c_count)
-    N = x.shape[0]
-    if out is None:
-        out = torch.empty((N, c_count), dtype=torch.float32, device=x.device)
-    elif out.shape != (N, c_count) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
-        raise ValueError("out must be a contiguous float32 [N, c_count] tensor on x's device")
+    x, c_begin, c_count, out, stream = _open(x, c_begin, c_count, out, half_ok=True, algo=algo, rows=None)
     if energy_route(x.shape, x.stride(), pad_front_if_odd, algo) == ROUTE_NHWC:
-        return _call_nhwc(x, c_begin, c_count, out)
+        return _call_nhwc(x, c_begin, c_count, out, stream)
+    x = _rows(x)
     if x.dtype != torch.float32:
-        return _call_half(x, c_begin, c_count, pad_front_if_odd, out)
-    return _call("dcts_energy_f32_ex", x, c_begin, c_count, pad_front_if_odd, out, algo)
+        return _call_half(x, c_begin, c_count, pad_front_if_odd, out, stream)
+    return _call("dcts_energy_f32_ex", x, c_begin, c_count, pad_front_if_odd, out, algo, stream)
 
 
 def dct2d(x, c_begin=0, c_count=None, pad_front_if_odd=False, algo=ALGO_AUTO):
     """Orthonormal 2-D DCT-II coefficients of every map -> [N, c_count, H', W'] fp32."""
-    _check_input(x)
-    c_begin, c_count = _slice(x, c_begin, c_count)
+    x, c_begin, c_count, _, stream = _open(x, c_begin, c_count, out=False)
     N, _, H, W = x.shape
     pad = 1 if (pad_front_if_odd and H % 2 == 1) else 0
     out = torch.empty((N, c_count, H + pad, W + pad), dtype=torch.float32, device=x.device)
-    return _call("dcts_dct2d_f32_ex", x, c_begin, c_count, pad_front_if_odd, out, algo)
+    return _call("dcts_dct2d_f32_ex", x, c_begin, c_count, pad_front_if_odd, out, algo, stream)
 
 
 def batch_sum(energy):
@@ -181,10 +192,20 @@ def batch_sum(energy):
     energy = energy.contiguous()
     out = torch.empty((energy.shape[1],), dtype=torch.float32, device=energy.device)
     stream = torch.cuda.current_stream(energy.device).cuda_stream
-    with torch.cuda.device(energy.device):
-        _lib.check(_lib.load().dcts_batch_sum_f32(energy.data_ptr(), energy.shape[0], energy.shape[1],
-                                                  out.data_ptr(), stream))
+    _launch(energy.device, _lib.load().dcts_batch_sum_f32, energy.data_ptr(), energy.shape[0], energy.shape[1],
+            out.data_ptr(), stream)
     return out
+
+
+def _pack_item(t, x, c_begin, c_count):
+    """Fills the dcts_tensor_item `t` for a channel slice of x; returns (x as the kernels read it, its [N, c_count]
+    output, the workspace bytes it needs)."""
+    x, c_begin, c_count, out, _ = _open(x, c_begin, c_count, rows="dense")
+    t.x, t.out_nc = x.data_ptr(), out.data_ptr()
+    t.N, t.C_total = x.shape[0], x.shape[1]
+    t.strideN, t.strideC = x.stride(0), x.stride(1)
+    t.c_begin, t.c_count = c_begin, c_count
+    return x, out, _lib.load().dcts_workspace_bytes(x.shape[0], c_count, x.shape[2], x.shape[3])
 
 
 def energy_multi(items, pad_front_if_odd=False):
@@ -201,25 +222,16 @@ def energy_multi(items, pad_front_if_odd=False):
     outs, keep = [], []
     need = 0
     for i, (x, c_begin, c_count) in enumerate(items):
-        _check_input(x)
+        x, out, nbytes = _pack_item(arr[i], x, c_begin, c_count)
         if x.shape[2] != H or x.shape[3] != W or x.device != dev:
             raise ValueError("energy_multi needs tensors of one tile shape on one device")
-        if x.stride(3) != 1 or x.stride(2) != W:
-            x = x.contiguous()
-        c_begin, c_count = _slice(x, c_begin, c_count)
-        out = torch.empty((x.shape[0], c_count), dtype=torch.float32, device=dev)
         keep.append(x)
         outs.append(out)
-        arr[i].x, arr[i].out_nc = x.data_ptr(), out.data_ptr()
-        arr[i].N, arr[i].C_total = x.shape[0], x.shape[1]
-        arr[i].strideN, arr[i].strideC = x.stride(0), x.stride(1)
-        arr[i].c_begin, arr[i].c_count = c_begin, c_count
-        need = max(need, lib.dcts_workspace_bytes(x.shape[0], c_count, H, W))
+        need = max(need, nbytes)
     stream = torch.cuda.current_stream(dev).cuda_stream
     ws = _workspace(dev, stream, need)
-    with torch.cuda.device(dev):
-        _lib.check(lib.dcts_energy_multi_f32(arr, len(items), H, W, 1 if pad_front_if_odd else 0,
-                                             ws.data_ptr(), ws.numel(), stream))
+    _launch(dev, lib.dcts_energy_multi_f32, arr, len(items), H, W, 1 if pad_front_if_odd else 0,
+            ws.data_ptr(), ws.numel(), stream)
     return outs
 
 
@@ -237,50 +249,33 @@ def energy_mixed(items):
     outs, keep = [], []
     need = 0
     for i, (x, c_begin, c_count, pad) in enumerate(items):
-        _check_input(x)
+        x, out, nbytes = _pack_item(arr[i].t, x, c_begin, c_count)
         if x.device != dev:
             raise ValueError("energy_mixed needs tensors on one device")
-        H, W = x.shape[2], x.shape[3]
-        if x.stride(3) != 1 or x.stride(2) != W:
-            x = x.contiguous()
-        c_begin, c_count = _slice(x, c_begin, c_count)
-        out = torch.empty((x.shape[0], c_count), dtype=torch.float32, device=dev)
         keep.append(x)
         outs.append(out)
-        t = arr[i].t
-        t.x, t.out_nc = x.data_ptr(), out.data_ptr()
-        t.N, t.C_total = x.shape[0], x.shape[1]
-        t.strideN, t.strideC = x.stride(0), x.stride(1)
-        t.c_begin, t.c_count = c_begin, c_count
-        arr[i].H, arr[i].W, arr[i].pad_front_if_odd = H, W, 1 if pad else 0
-        need = max(need, lib.dcts_workspace_bytes(x.shape[0], c_count, H, W))
+        arr[i].H, arr[i].W, arr[i].pad_front_if_odd = x.shape[2], x.shape[3], 1 if pad else 0
+        need = max(need, nbytes)
     stream = torch.cuda.current_stream(dev).cuda_stream
     ws = _workspace(dev, stream, need)
-    with torch.cuda.device(dev):
-        _lib.check(lib.dcts_energy_mixed_f32(arr, len(items), ws.data_ptr(), ws.numel(), stream))
+    _launch(dev, lib.dcts_energy_mixed_f32, arr, len(items), ws.data_ptr(), ws.numel(), stream)
     return outs
 
 
 def weighted_energy_nc(x, weights, c_begin=0, c_count=None, pad_front_if_odd=False):
     """Coefficient-domain score variant: E[n, j] = sum_{u,v} weights[u,v] * dct_2d(x[n, c_begin+j])[u,v]**2.
     `weights`: [H', W'] fp32 on x's device (H' = H + 1 for an odd H with pad_front_if_odd). All ones gives energy_nc."""
-    _check_input(x)
-    c_begin, c_count = _slice(x, c_begin, c_count)
+    x, c_begin, c_count, out, stream = _open(x, c_begin, c_count)
     N, C, H, W = x.shape
     pad = 1 if (pad_front_if_odd and H % 2 == 1) else 0
     if weights.shape != (H + pad, W + pad) or weights.dtype != torch.float32 or weights.device != x.device:
         raise ValueError("weights must be a float32 [%d, %d] tensor on %s" % (H + pad, W + pad, x.device))
-    if x.stride(3) != 1 or x.stride(2) < W:
-        x = x.contiguous()
     weights = weights.contiguous()
     lib = _lib.load()
-    out = torch.empty((N, c_count), dtype=torch.float32, device=x.device)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
     ws = _workspace(x.device, stream, lib.dcts_weighted_workspace_bytes(N, c_count, H, W))
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dcts_weighted_energy_f32(
+    _launch(x.device, lib.dcts_weighted_energy_f32,
             x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3), c_begin, c_count,
-            1 if pad_front_if_odd else 0, weights.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+            1 if pad_front_if_odd else 0, weights.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
     return out
 
 
@@ -295,25 +290,20 @@ def band_energy_nc(x, weights, c_begin=0, c_count=None, pad_front_if_odd=False, 
     pad_front_if_odd); one-hot weights (bands.partition) give the energy of K frequency bands.
     algo: ALGO_AUTO (fused kernel where it exists, else the fallback), ALGO_CODELET (fused only), ALGO_DIRECT
     (fallback only). Enqueues on the current stream of x's device; no synchronisation."""
-    _check_input(x)
-    c_begin, c_count = _slice(x, c_begin, c_count)
+    x, c_begin, c_count, _, stream = _open(x, c_begin, c_count, out=False)
     N, C, H, W = x.shape
     pad = 1 if (pad_front_if_odd and H % 2 == 1) else 0
     if (not isinstance(weights, torch.Tensor) or weights.dim() != 3 or tuple(weights.shape[1:]) != (H + pad, W + pad)
             or weights.dtype != torch.float32 or weights.device != x.device):
         raise ValueError("weights must be a float32 [K, %d, %d] tensor on %s" % (H + pad, W + pad, x.device))
     K = weights.shape[0]
-    if x.stride(3) != 1 or x.stride(2) < W:
-        x = x.contiguous()
     weights = weights.contiguous()
     lib = _lib.load()
     out = torch.empty((N, c_count, K), dtype=torch.float32, device=x.device)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
     ws = _workspace(x.device, stream, max(lib.dcts_band_workspace_bytes(N, c_count, H, W, K), 16))
-    with torch.cuda.device(x.device):
-        _lib.check(lib.dcts_band_energy_f32(
+    _launch(x.device, lib.dcts_band_energy_f32,
             x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3), c_begin, c_count,
-            1 if pad_front_if_odd else 0, weights.data_ptr(), K, out.data_ptr(), ws.data_ptr(), ws.numel(), stream, algo))
+            1 if pad_front_if_odd else 0, weights.data_ptr(), K, out.data_ptr(), ws.data_ptr(), ws.numel(), stream, algo)
     return out
 
 
@@ -331,28 +321,18 @@ def spectral_entropy_nc(x, c_begin=0, c_count=None, pad_front_if_odd=False, algo
     algo: ALGO_AUTO (fused kernel where it exists, else the fallback), ALGO_CODELET (fused only), ALGO_DIRECT
     (fallback only). float32 NCHW only; a tensor whose rows are not W-contiguous is copied with .contiguous() first.
     Enqueues on the current stream of x's device; no synchronisation."""
-    _check_input(x)
-    c_begin, c_count = _slice(x, c_begin, c_count)
+    x, c_begin, c_count, out, stream = _open(x, c_begin, c_count, out)
     N, C, H, W = x.shape
-    if out is None:
-        out = torch.empty((N, c_count), dtype=torch.float32, device=x.device)
-    elif out.shape != (N, c_count) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
-        raise ValueError("out must be a contiguous float32 [N, c_count] tensor on x's device")
-    if x.stride(3) != 1 or x.stride(2) < W:
-        x = x.contiguous()
     lib = _lib.load()
-    stream = torch.cuda.current_stream(x.device).cuda_stream
     nbytes = lib.dcts_entropy_workspace_bytes(N, c_count, H, W)
     if nbytes == 0 and (x.stride(2) != W or algo == ALGO_DIRECT):
         # a fused shape that takes the fallback: sized as the header says, for (H, W + 1)
         nbytes = lib.dcts_entropy_workspace_bytes(N, c_count, H, W + 1)
     ws = _workspace(x.device, stream, nbytes) if nbytes else None
-    with torch.cuda.device(x.device):
-        code = lib.dcts_spectral_entropy_f32(
+    _launch(x.device, lib.dcts_spectral_entropy_f32,
             x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3), c_begin, c_count,
             1 if pad_front_if_odd else 0, out.data_ptr(), ws.data_ptr() if nbytes else None, ws.numel() if nbytes else 0,
             stream, algo)
-    _lib.check(code)
     return out
 
 
@@ -363,18 +343,8 @@ def rank_nc(x, c_begin=0, c_count=None, out=None):
     torch.linalg.matrix_rank for fp32, computed in fp64. Edges up to 64 on each axis.
     Enqueues on the current stream of x's device; no synchronisation.
     """
-    _check_input(x)
-    c_begin, c_count = _slice(x, c_begin, c_count)
+    x, c_begin, c_count, out, stream = _open(x, c_begin, c_count, out)
     N, C, H, W = x.shape
-    if out is None:
-        out = torch.empty((N, c_count), dtype=torch.float32, device=x.device)
-    elif out.shape != (N, c_count) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
-        raise ValueError("out must be a contiguous float32 [N, c_count] tensor on x's device")
-    if x.stride(3) != 1 or x.stride(2) < W:
-        x = x.contiguous()
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    with torch.cuda.device(x.device):
-        code = _lib.load().dcts_rank_f32(x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
-                                         c_begin, c_count, out.data_ptr(), stream)
-    _lib.check(code)
+    _launch(x.device, _lib.load().dcts_rank_f32, x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+            c_begin, c_count, out.data_ptr(), stream)
     return out

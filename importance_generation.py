@@ -6,21 +6,15 @@ importance_score/<net>_limit<L>/*.npy under the current directory, which prune_c
 prune_imagenet.py / prune_u2netp.py read through --imp_score. The DCT+score arithmetic runs
 in libdctscore (HIP, gfx950); a GPU is required.
 
-Extra, opt-in flags: --synthetic (seeded synthetic batches; also lifts the need for a
-checkpoint), --input_size, --seed, --single_sweep, --device_accumulate, --deferred, --criterion {dct,rank,bands,entropy}
-(rank: HRank's feature-map rank instead of the DCT energy, written to rank_conv/<net>_limit<L>/rank_*.npy;
-edges up to 64, so not with --net u2netp, and not with --deferred; bands: the DCT energy of K frequency bands per
-channel, --bands K --band_kind {square,diag}, a [C, K] spectrum per hook point under
-band_score/<net>_limit<L>_<kind><K>/band_*.npy that `python -m dct_pruning_amd.bands` collapses into imp_*.npy for any
-band weighting; not with --deferred; entropy: the spectral entropy of every map's DCT coefficients, one number per
-channel that depends on the transform, written to entropy_score/<net>_limit<L>/ent_*.npy, which
-`python -m dct_pruning_amd.masks` and prune_*.py --imp_score read as they are; every net; not with --deferred,
---autocast or --channels_last), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
-half-precision feature maps are scored as they are, without an upcast copy; same files, the scores are those of the
-autocast forward pass; --criterion dct only, not with --deferred), --channels_last (the net and its inputs run in
-torch.channels_last and the feature maps are scored in the layout they arrive in, without a transposing copy where a
-channels-last kernel exists; same files; combines with --autocast; --criterion dct only, not with --deferred or
---net u2netp). Multi-GPU: launch with
+Extra, opt-in flags: --synthetic (seeded synthetic batches; also lifts the need for a checkpoint), --input_size,
+--seed, --single_sweep, --device_accumulate, --deferred, --criterion (what is scored and where it goes:
+the DCT energy under importance_score/, HRank's feature-map rank under rank_conv/, the DCT energy of K frequency bands
+per channel, --bands K --band_kind {square,diag}, under band_score/, or the spectral entropy of the DCT coefficients
+under entropy_score/), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
+half-precision feature maps are scored as they are) and --channels_last (the net and its inputs run in
+torch.channels_last and the feature maps are scored in the layout they arrive in). dct_pruning_amd/harness.py says
+what each criterion writes and which of these modes and nets it supports (its criterion table and check_options, which
+also rejects the command lines here). Multi-GPU: launch with
 `python -m torch.distributed.run --nproc-per-node G importance_generation.py ...` — hook points
 are sharded over the ranks and rank 0 writes the files.
 """
@@ -30,7 +24,7 @@ from collections import OrderedDict
 
 import torch
 
-from dct_pruning_amd import harness, nets
+from dct_pruning_amd import bands, harness, nets
 
 
 def parse_args(argv=None):
@@ -52,11 +46,11 @@ def parse_args(argv=None):
     parser.add_argument("--device_accumulate", action="store_true", help="keep the running mean on the GPU")
     parser.add_argument("--deferred", action="store_true",
                         help="single sweep, one scoring launch per tile shape per batch (implies the two above)")
-    parser.add_argument("--criterion", type=str, default="dct", choices=("dct", "rank", "bands", "entropy"),
+    parser.add_argument("--criterion", type=str, default="dct", choices=harness.CRITERIA,
                         help="dct: DCT energy (importance_score/); rank: HRank feature-map rank (rank_conv/); "
                              "bands: DCT energy per frequency band (band_score/); "
                              "entropy: spectral entropy of the DCT coefficients (entropy_score/)")
-    parser.add_argument("--bands", type=int, default=4, help="--criterion bands: number of bands K, 1 ... 8")
+    parser.add_argument("--bands", type=int, default=4, help="--criterion bands: number of bands K, 1 ... %d" % bands.BAND_MAX)
     parser.add_argument("--band_kind", type=str, default="square", choices=("square", "diag"),
                         help="--criterion bands: L-infinity shells (square) or anti-diagonal stripes (diag)")
     parser.add_argument("--autocast", type=str, default=None, choices=("fp16", "bf16"),
@@ -64,26 +58,11 @@ def parse_args(argv=None):
     parser.add_argument("--channels_last", action="store_true",
                         help="run the net and its inputs in torch.channels_last and score the feature maps in that layout")
     args = parser.parse_args(argv)
-    if args.channels_last and args.deferred:
-        parser.error("--channels_last has no --deferred mode (use --single_sweep / --device_accumulate)")
-    if args.channels_last and args.criterion != "dct":
-        parser.error("--channels_last supports --criterion dct only")
-    if args.channels_last and args.net == "u2netp":
-        parser.error("--channels_last does not cover --net u2netp")
-    if args.autocast and args.deferred:
-        parser.error("--autocast has no --deferred mode (use --single_sweep / --device_accumulate)")
-    if args.autocast and args.criterion != "dct":
-        parser.error("--autocast supports --criterion dct only")
-    if args.criterion == "rank" and args.net == "u2netp":
-        parser.error("--criterion rank supports feature maps up to 64 x 64; --net u2netp is out of its scope")
-    if args.criterion == "rank" and args.deferred:
-        parser.error("--criterion rank has no --deferred mode (use --single_sweep / --device_accumulate)")
-    if args.criterion == "bands" and args.deferred:
-        parser.error("--criterion bands has no --deferred mode (use --single_sweep / --device_accumulate)")
-    if args.criterion == "entropy" and args.deferred:
-        parser.error("--criterion entropy has no --deferred mode (use --single_sweep / --device_accumulate)")
-    if args.criterion == "bands" and not 1 <= args.bands <= 8:
-        parser.error("--bands must be between 1 and 8")
+    try:
+        harness.check_options(args.criterion, args.net, args.deferred, args.autocast, args.channels_last,
+                              (args.bands, args.band_kind))
+    except ValueError as e:
+        parser.error(str(e))
     return args
 
 
