@@ -8,7 +8,7 @@
 // 2-D DCT-II and the squared coefficients are reduced to one fp32 energy per map.
 //
 // The kernel families are units of their own (codelet.hip, split.hip, fused.hip, fused2.hip, pipe.hip, tile2d.hip,
-// tile2g.hip, rect.hip, rank.hip, band.hip, entropy.hip, half.hip, nhwc.hip, direct.hip: the cosine-matrix fallback for any
+// tile2g.hip, rect.hip, rank.hip, band.hip, entropy.hip, gm.hip, half.hip, nhwc.hip, direct.hip: the cosine-matrix fallback for any
 // (H, W) <= DCTS_MAX_EDGE, reduce.hip: batch sum, running mean, weighted reduction). What stays here of the direct family is
 // the memo of its basis tables: which workspace holds which tables is host policy.
 #include <hip/hip_runtime.h>
@@ -622,6 +622,22 @@ int dcts_spectral_entropy_f32(const float* x, int64_t N, int64_t C_total, int64_
   return coeff_fallback(v, workspace, workspace_bytes, stream, [&](int64_t nmaps, int64_t first) {
     return launch_entropy_reduce(reinterpret_cast<float*>(workspace), nmaps, HP * WP, out_nc + first, st);
   });
+}
+
+// ---- the summed distance of every scored map to a reference set (gm.hip) ------------------------------------------------
+// Two channel ranges, each checked as the scored one of every other entry; then the common checks on the scored range. Dense
+// maps only: a row pitch is the caller's copy. No workspace, no host state.
+int dcts_gm_distance_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN, int64_t strideC,
+                         int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count, int32_t r_begin, int32_t r_count,
+                         float* out_nc, void* stream) {
+  const TensorView v = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, /*pad_front_if_odd=*/0);
+  const TensorView r = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, r_begin, r_count, /*pad_front_if_odd=*/0);
+  if (const int rc = validate(v, {out_nc}, Checks::Channels)) return rc;
+  if (const int rc = validate(r, {out_nc}, Checks::Channels)) return rc;
+  if (const int rc = validate(v, {out_nc}, Checks::All)) return rc;
+  if (!v.dense_rows()) return DCTS_E_UNSUPPORTED;  // strideH > W
+  return dispatch_gm(GmGeom{x, N, strideN, strideC, c_begin, c_count, r_begin, r_count, (int)(H * W)}, out_nc,
+                     reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- fp16 / bf16 inputs (half.hip) -----------------------------------------------------------------------------------

@@ -181,6 +181,19 @@ int dispatch_entropy(int HP, int pad, const MapGeom& g, float* out, hipStream_t 
 // fallback reduction: out[m] = entropy of the squares of `nmaps` dense tiles of `hw` coefficients (any common scale)
 int launch_entropy_reduce(const float* coeff, long long nmaps, int hw, float* out, hipStream_t st);
 
+// ---- gm.hip: summed distance of every scored map to the maps of a reference set (dcts_gm_distance_f32) -----------------
+// Dense maps of hw = H * W elements; the scored channels [c_begin, c_begin + c_count) and the reference channels
+// [r_begin, r_begin + r_count) of every sample. One launch, no workspace.
+struct GmGeom {
+  const float* x;
+  long long N;
+  long long strideN, strideC;  // elements
+  int c_begin, c_count;
+  int r_begin, r_count;
+  int hw;
+};
+int dispatch_gm(const GmGeom& g, float* out, hipStream_t st);
+
 // ---- half.hip: fp16 / bf16 inputs (dcts_energy_typed) -------------------------------------------------------------
 // MapGeom for 2-byte elements (raw bits; the dtype travels beside it). Rows are dense: strideH == W.
 struct HalfGeom {

@@ -67,6 +67,17 @@ constexpr int kLaneMultiWaves = 2;
 constexpr int kLaneMultiGroup = 64;
 constexpr int kMixedWaves = 4;
 
+// gm.hip, k_gm_distance: a workgroup of kGmThreads threads owns one sample and kGmTS scored channels, walks the reference set
+// kGmTR channels at a time and the flattened H * W axis kGmKP elements at a time; kGmLD: floats per channel row of its LDS
+// image. One workgroup per (sample, scored tile) and no grid-stride loop: kGmMaxBlocks is the largest grid.x there is,
+// and a call that would need more is refused (DCTS_E_SHAPE)
+constexpr int kGmThreads = 256;
+constexpr int kGmTS = 64;
+constexpr int kGmTR = 64;
+constexpr int kGmKP = 64;
+constexpr int kGmLD = kGmKP + 4;
+constexpr long long kGmMaxBlocks = 0x7fffffffLL;
+
 // nhwc.hip: waves per workgroup of the lane = channel kernel (a wave takes 64 channels of one sample), and the channels a
 // workgroup of the block kernel (edges 14 ... 32) and of the strip kernel (edge 56) takes
 constexpr int kNhwcLaneWaves = 4;

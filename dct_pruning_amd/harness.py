@@ -36,6 +36,12 @@ Additions (opt-in, results identical on fixed batches):
                       number per map, higher = richer, through the same hooks, accumulators, schedules and sharding;
                       files go to entropy_score/<net>_limit<L>/ent_*.npy (hooks get_feature_hook_entropy /
                       get_feature_hook_densenet_entropy / get_feature_hook_u2net_input_entropy);
+  criterion="gm"      the geometric-median criterion on feature maps (dcts_gm_distance_f32, ops.gm_distance_nc): the summed
+                      distance of every map to the maps of the channels that compete for its mask (every channel for the
+                      "full" and "input" hooks, the last 12 for "last12"), high = far from the others = keep; the one
+                      criterion that looks at a second channel. No odd pad (it changes no distance). Files go to
+                      gm_score/<net>_limit<L>/gm_*.npy (hooks get_feature_hook_gm / get_feature_hook_densenet_gm /
+                      get_feature_hook_u2net_input_gm);
   autocast="fp16" | "bf16"
                       the forward sweeps run under torch.autocast; the hooks hand the tensors to ops.energy_nc in
                       whatever dtype arrives (float16 / bfloat16 maps are scored natively, dcts_energy_typed; a tensor
@@ -45,7 +51,8 @@ Additions (opt-in, results identical on fixed batches):
                       layout arrives and ops.energy_nc reads channels-last tensors where they lie (dcts_energy_nhwc).
                       Same files. Combines with autocast. The "dct" criterion only, not with deferred=True, not u2netp.
 
-A criterion is defined in one place here: its scorer `_score_<name>(x, c_begin, c_count, pad)` and its row of the
+A criterion is defined in one place here: its scorer `_score_<name>(x, c_begin, c_count, pad)` (a cross-channel one takes
+`ref=(begin, count)`, the hook kind's whole channel set, as well) and its row of the
 criterion table below it (output root and file prefix, hook kinds and odd pad, score width, LPT cost, supported modes and
 excluded nets). The hooks, _PointHook, imp_score, check_options and importance_generation.py's parser read the row, so
 adding a criterion takes an operator in ops.py, a scorer, a row, and tests and docs for it.
@@ -66,6 +73,7 @@ _energy_nc = ops.energy_nc
 _rank_nc = ops.rank_nc
 _band_energy_nc = ops.band_energy_nc
 _entropy_nc = ops.spectral_entropy_nc
+_gm_nc = ops.gm_distance_nc
 
 AUTOCAST = {"fp16": torch.float16, "bf16": torch.bfloat16}
 
@@ -104,6 +112,12 @@ def _score_entropy(x, c_begin, c_count, pad):
     return _entropy_nc(x, c_begin=c_begin, c_count=c_count, pad_front_if_odd=pad)
 
 
+def _score_gm(x, c_begin, c_count, pad, ref):
+    """The summed distance to the maps of `ref` = (begin, count), the hook kind's whole channel set, whichever channel range
+    of it is scored here (no odd pad: zeros in front of both maps change no distance)."""
+    return _gm_nc(x, c_begin=c_begin, c_count=c_count, ref_begin=ref[0], ref_count=ref[1])
+
+
 # A criterion is its scorer above and its row here; everything below reads the row.
 #   root, prefix  output root under the CWD; the file stem is the schedule's with its leading imp_ replaced by `prefix`
 #                 (a stem without imp_, U2-Net-p's net.<module path>, gets it in front); None keeps the stem
@@ -112,9 +126,11 @@ def _score_entropy(x, c_begin, c_count, pad):
 #   banded        scores are [N, c, K] for the K of bands=(K, kind): files hold [C, K], the output dir ends in _<kind><K>
 #   cost          LPT cost of one channel of an H x W hook point: the bytes the DCT kernels stream, or the kernel's arithmetic
 #   deferred, autocast, channels_last   the modes it supports; `excluded`: {net: why it is out of scope}
+#   cross         the score of a map depends on other channels: the scorer also takes ref=(begin, count), the channels of the
+#                 hook kind (_kind_slice), which stay whole when a hook point is scored in channel ranges
 Criterion = collections.namedtuple(
-    "Criterion", "name root prefix score what kinds pad banded cost deferred autocast channels_last excluded",
-    defaults=(("full", "last12", "input"), True, False, lambda H, W: H * W, False, False, False, {}))
+    "Criterion", "name root prefix score what kinds pad banded cost deferred autocast channels_last excluded cross",
+    defaults=(("full", "last12", "input"), True, False, lambda H, W: H * W, False, False, False, {}, False))
 _TABLE = {c.name: c for c in (
     Criterion("dct", "importance_score", None, _score_dct, "the DCT energy of every map",
               deferred=True, autocast=True, channels_last=True),
@@ -127,6 +143,9 @@ _TABLE = {c.name: c for c in (
               "the DCT energy split into K bands: the accumulator's view(a, -1).sum(0) runs over the flat [a, C*K] view, "
               "so feature_result is the [C, K] spectrum in row-major order", banded=True),
     Criterion("entropy", "entropy_score", "ent_", _score_entropy, "the spectral entropy of every map"),
+    Criterion("gm", "gm_score", "gm_", _score_gm,
+              "the summed distance of every map to the maps of the hook's channels (the geometric-median criterion)",
+              pad=False, cross=True),
 )}
 CRITERIA = tuple(_TABLE)
 
@@ -152,7 +171,15 @@ def _kind_slice(crit, kind, C):
 def _hook_score(criterion, kind, x):
     """The scores of every map the hook of that kind scores."""
     crit = _TABLE[criterion]
-    return crit.score(x, *_kind_slice(crit, kind, x.shape[1]))
+    base, count, pad = _kind_slice(crit, kind, x.shape[1])
+    return _score(crit, x, base, count, pad, (base, count))
+
+
+def _score(crit, x, c_begin, c_count, pad, ref):
+    """The criterion's scorer on a channel range; `ref`: the hook kind's whole range, which a cross-channel criterion needs."""
+    if crit.cross:
+        return crit.score(x, c_begin, c_count, pad, ref=ref)
+    return crit.score(x, c_begin, c_count, pad)
 
 
 def _hook_energy(kind, x):
@@ -273,7 +300,7 @@ def _done_line(net_name, idx, stem):
 
 
 def _file_stem(criterion, stem):
-    """The schedule's stem under the criterion's prefix: imp_conv3 -> rank_conv3 / band_conv3 / ent_conv3, U2-Net-p's
+    """The schedule's stem under the criterion's prefix: imp_conv3 -> rank_conv3 / band_conv3 / ent_conv3 / gm_conv3, U2-Net-p's
     net.<module path> -> band_net.<module path>; "dct" keeps the stem."""
     prefix = _TABLE[criterion].prefix
     if prefix is None:
@@ -297,7 +324,8 @@ class _PointHook:
     `ranges` (multi-GPU, single-sweep modes): the channel ranges [(key, lo, hi), ...] of this hook point's
     scored channels that THIS rank owns (sharding.make_units cuts wide layers so that eight ranks balance);
     None = the whole hook point under `key`. Per-channel scores do not depend on which call computes them,
-    so the pieces concatenate to the unsplit result bit for bit."""
+    so the pieces concatenate to the unsplit result bit for bit (a cross-channel criterion's pieces are all scored against
+    the hook kind's whole channel set)."""
 
     def __init__(self, kind, accumulate, device, batch=None, key=None, deferred=False, ranges=None, nominal_c=None,
                  criterion="dct"):
@@ -321,11 +349,12 @@ class _PointHook:
 
     def __call__(self, module, inputs, output):
         x = _scored_tensor(self.kind, inputs, output)
+        ref = _kind_slice(self.crit, self.kind, x.shape[1])[:2]
         for key, cb, cc, pad in self._pieces(x):
             if self.deferred and self.batch is not None:
                 self.batch.add_tensor(key, x, cb, cc, pad)
                 continue
-            e = self.crit.score(x, cb, cc, pad)
+            e = _score(self.crit, x, cb, cc, pad, ref)
             if e.dim() == 3:  # [N, c, K] band energies: the accumulators see the dense [N, c*K] view
                 self.width = e.shape[2]
                 e = e.reshape(e.shape[0], -1)
@@ -406,7 +435,8 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
     DCT energy and writes rank_conv/<net>_limit<L>/rank_*.npy. criterion="bands" with bands=(K, kind) writes the
     [C, K] band spectrum of every hook point to band_score/<net>_limit<L>_<kind><K>/band_*.npy. criterion="entropy"
     scores the spectral entropy of every map's DCT coefficients and writes entropy_score/<net>_limit<L>/ent_*.npy (all
-    seven nets; not with deferred, autocast or channels_last).
+    seven nets; not with deferred, autocast or channels_last). criterion="gm" scores every map's summed distance to the
+    maps of its hook's channels and writes gm_score/<net>_limit<L>/gm_*.npy (all seven nets; same exclusions).
     autocast="fp16" / "bf16" runs the forward sweeps under torch.autocast and scores the half-precision tensors the
     hooks then see as they are (criterion "dct" only, not with deferred).
     channels_last=True converts the net (in place) and every input batch to torch.channels_last; the tensors the hooks

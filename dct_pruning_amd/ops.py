@@ -348,3 +348,22 @@ def rank_nc(x, c_begin=0, c_count=None, out=None):
     _launch(x.device, _lib.load().dcts_rank_f32, x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
             c_begin, c_count, out.data_ptr(), stream)
     return out
+
+
+def gm_distance_nc(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, out=None):
+    """G[n, j] = sum_k ||x[n, c_begin+j] - x[n, k]||_2 over the reference channels k in [ref_begin, ref_begin + ref_count)
+    -> [N, c_count] fp32 (ref_count None = to the end).
+
+    The geometric-median criterion on feature maps (dcts_gm_distance_f32): the summed Euclidean distance (over the H * W
+    elements) of every scored map to the maps of the reference set of its sample. A map close to the others, one they can
+    stand in for, scores low; high = keep. Computed in the difference form: the term of a map with itself is exactly 0, two
+    identical maps are at distance +0.0, and pieces of a channel range scored against the same reference set concatenate
+    to the unsplit result bit for bit. There is no odd front pad: zeros in front of both maps change no distance.
+    float32 NCHW only; a tensor whose maps are not dense (stride(3) != 1 or stride(2) != W) is copied with .contiguous()
+    first. Enqueues on the current stream of x's device; no synchronisation."""
+    x, c_begin, c_count, out, stream = _open(x, c_begin, c_count, out, rows="dense")
+    ref_begin, ref_count = _slice(x, ref_begin, ref_count)
+    N, C, H, W = x.shape
+    _launch(x.device, _lib.load().dcts_gm_distance_f32, x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+            c_begin, c_count, ref_begin, ref_count, out.data_ptr(), stream)
+    return out

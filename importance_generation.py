@@ -9,8 +9,9 @@ in libdctscore (HIP, gfx950); a GPU is required.
 Extra, opt-in flags: --synthetic (seeded synthetic batches; also lifts the need for a checkpoint), --input_size,
 --seed, --single_sweep, --device_accumulate, --deferred, --criterion (what is scored and where it goes:
 the DCT energy under importance_score/, HRank's feature-map rank under rank_conv/, the DCT energy of K frequency bands
-per channel, --bands K --band_kind {square,diag}, under band_score/, or the spectral entropy of the DCT coefficients
-under entropy_score/), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
+per channel, --bands K --band_kind {square,diag}, under band_score/, the spectral entropy of the DCT coefficients
+under entropy_score/, or every map's summed distance to the other maps of its layer, the geometric-median criterion, under
+gm_score/), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
 half-precision feature maps are scored as they are) and --channels_last (the net and its inputs run in
 torch.channels_last and the feature maps are scored in the layout they arrive in). dct_pruning_amd/harness.py says
 what each criterion writes and which of these modes and nets it supports (its criterion table and check_options, which
@@ -49,7 +50,8 @@ def parse_args(argv=None):
     parser.add_argument("--criterion", type=str, default="dct", choices=harness.CRITERIA,
                         help="dct: DCT energy (importance_score/); rank: HRank feature-map rank (rank_conv/); "
                              "bands: DCT energy per frequency band (band_score/); "
-                             "entropy: spectral entropy of the DCT coefficients (entropy_score/)")
+                             "entropy: spectral entropy of the DCT coefficients (entropy_score/); "
+                             "gm: summed distance to the other maps of the layer, geometric median (gm_score/)")
     parser.add_argument("--bands", type=int, default=4, help="--criterion bands: number of bands K, 1 ... %d" % bands.BAND_MAX)
     parser.add_argument("--band_kind", type=str, default="square", choices=("square", "diag"),
                         help="--criterion bands: L-infinity shells (square) or anti-diagonal stripes (diag)")

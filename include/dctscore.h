@@ -48,7 +48,8 @@ extern "C" {
  *    additive, and a library that lacks them fails at symbol lookup. The same holds for the fp16 / bf16 entry points
  *    (dcts_energy_typed, dcts_typed_workspace_bytes, dcts_has_half_kernel, DCTS_DTYPE_*) and for the channels-last ones
  *    (dcts_energy_nhwc, dcts_nhwc_workspace_bytes, dcts_has_nhwc_kernel), and for the spectral-entropy ones
- *    (dcts_spectral_entropy_f32, dcts_entropy_workspace_bytes, dcts_has_entropy_kernel). */
+ *    (dcts_spectral_entropy_f32, dcts_entropy_workspace_bytes, dcts_has_entropy_kernel), and for the geometric-median
+ *    criterion's entry point (dcts_gm_distance_f32). */
 #define DCTS_ABI_VERSION 3
 
 enum {
@@ -248,6 +249,39 @@ int dcts_spectral_entropy_f32(const float* x, int64_t N, int64_t C_total, int64_
                               int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
                               int32_t c_begin, int32_t c_count, int32_t pad_front_if_odd,
                               float* out_nc, void* workspace, size_t workspace_bytes, void* stream, int32_t algo);
+
+/*
+ * The geometric-median criterion on feature maps (gm.hip): FPGM prunes the filter whose weights lie closest to the geometric
+ * median of its layer, the element whose summed distance to all the others is smallest. Applied to the maps a layer produces:
+ *
+ *     out_nc[n*c_count + j] = sum_{k = r_begin}^{r_begin+r_count-1} || x[n, c_begin+j] - x[n, k] ||_2     [N, c_count] fp32, dense
+ *
+ * the Euclidean norm over the H * W elements of a map. High = far from the other maps of the reference set = keep, so "keep
+ * the highest scores" holds as for every other criterion. The only entry point whose value looks at a second channel.
+ *   c_begin, c_count    the scored maps;  r_begin, r_count   the reference set they are compared with. Both ranges lie inside
+ *              [0, C_total) (DCTS_E_CHANNELS otherwise). They are separate so that a caller who cuts a layer into channel ranges
+ *              can still compare every piece with the whole layer.
+ *   x, strides   addressed as for dcts_energy_f32, but the maps must be dense: strideW == 1 and strideH == W (strideW != 1 or
+ *              strideH < W: DCTS_E_STRIDE; strideH > W: DCTS_E_UNSUPPORTED, the copy stays with the caller). strideN and
+ *              strideC may be anything; x any 4-byte-aligned address (DCTS_E_ALIGN otherwise). Any 1 <= H, W <= DCTS_MAX_EDGE.
+ *              All offsets are computed in 64 bits. One workgroup serves a sample and 64 scored channels; a call that needs
+ *              more than 2^31 - 1 of them returns DCTS_E_SHAPE.
+ *   There is no pad_front_if_odd: a zero row and a zero column in front of BOTH maps add zeros to the sum of squared
+ *              differences, so the odd front pad is a no-op by construction.
+ * Arithmetic, all fp32 VALU: the DIFFERENCE form d^2 = sum_p (a_p - b_p)^2, one fused multiply-add chain per pair with p
+ * ascending, d = sqrtf(d^2), then a fixed-order sum over k. Never the Gram form |a|^2 + |b|^2 - 2 a.b, which cancels for the
+ * near-duplicate pairs the criterion exists to find. Hence: the k == c term is exactly 0; two identical maps are at distance
+ * exactly +0.0; an all-zero sample gives +0.0 everywhere; d(a, b) has the same bits whichever map is scored and whichever is
+ * the reference.
+ * out[n, j] depends on the scored map and on the reference set of sample n only: not on N, not on c_begin / c_count (pieces
+ * of a channel range concatenate to the unsplit result bit for bit), not on the map's position in a tile or the launch
+ * count. No atomics. A NaN / Inf map poisons the outputs of its own sample only (it is a term of each of them).
+ * No workspace, no host state; only enqueues on `stream`; the arguments are checked before any launch.
+ */
+int dcts_gm_distance_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                         int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
+                         int32_t c_begin, int32_t c_count, int32_t r_begin, int32_t r_count,
+                         float* out_nc, void* stream);
 
 /*
  * dcts_energy_f32 for feature maps of another element type: what a forward pass under autocast hands to a hook.

@@ -1,0 +1,61 @@
+#!/usr/bin/env python3
+"""The geometric-median kernel (k_gm_distance, gm.hip) at the hook shapes of ResNet-50 at batch 256 and at U2-Net-p's
+64 x 288 x 288 at batch 12: every call scores all channels of a post-ReLU normal tensor against all of them and is timed
+with a pair of HIP events on the launch stream; the median of --reps calls (default 21) after two warm-up calls is
+reported. One JSON line per shape.
+
+The kernel is compute-bound (every element loaded is used against 64 maps), so the input is one buffer, not rotated.
+pair_elems = N * C * C * H * W element pairs per call; each costs two fp32 VALU operations in the difference form (a
+subtract and a fused multiply-add): valu_ops = 2 * pair_elems. Reported: pair elements per second, and valu_ops per second
+as a share of the 157.3e12 of the MI355X's fp32 vector peak. That peak counts a packed fma as four operations (two lanes'
+multiply and add): one operation (a subtract or an fma) per lane and clock is 39.3e12 per second at 2.4 GHz, a share of 0.25.
+usage: tools/microbench_gm.py [--reps R] [N,C,H,W ...]"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import dct_pruning_amd as dpa  # noqa: E402
+
+SHAPES = [(256, 256, 56, 56), (256, 512, 28, 28), (256, 1024, 14, 14), (256, 2048, 7, 7), (12, 64, 288, 288)]
+PEAK_FP32_VECTOR = 157.3e12
+WARMUP = 2
+
+
+def run(shape, reps):
+    n, c, h, w = shape
+    x = torch.relu(torch.randn(n, c, h, w, device="cuda"))
+    out = torch.empty(n, c, device="cuda")
+    for _ in range(WARMUP):
+        dpa.gm_distance_nc(x, out=out)
+    torch.cuda.synchronize()
+    pairs = []
+    for _ in range(reps):
+        a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        dpa.gm_distance_nc(x, out=out)
+        z.record()
+        pairs.append((a, z))
+    torch.cuda.synchronize()
+    ts = sorted(a.elapsed_time(z) for a, z in pairs)  # ms
+    med = ts[len(ts) // 2]
+    pair_elems = n * c * c * h * w
+    workgroups = n * -(-c // 64)
+    res = {"shape": list(shape), "reps": reps, "workgroups": workgroups, "median_ms": round(med, 3), "min_ms": round(ts[0], 3),
+           "max_ms": round(ts[-1], 3), "pair_elems": pair_elems, "pair_elems_per_s": round(pair_elems / med * 1e3, 1),
+           "valu_ops_per_s": round(2 * pair_elems / med * 1e3, 1),
+           "share_of_fp32_vector_peak": round(2 * pair_elems / med * 1e3 / PEAK_FP32_VECTOR, 4),
+           "input_gbps": round(x.numel() * 4 / med / 1e6, 1)}
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=21)
+    ap.add_argument("shapes", nargs="*")
+    a = ap.parse_args()
+    for s in [tuple(int(v) for v in s.split(",")) for s in a.shapes] or SHAPES:
+        run(s, a.reps)
