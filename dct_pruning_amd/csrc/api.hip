@@ -627,17 +627,54 @@ int dcts_spectral_entropy_f32(const float* x, int64_t N, int64_t C_total, int64_
 // ---- the summed distance of every scored map to a reference set (gm.hip) ------------------------------------------------
 // Two channel ranges, each checked as the scored one of every other entry; then the common checks on the scored range. Dense
 // maps only: a row pitch is the caller's copy. No workspace, no host state.
-int dcts_gm_distance_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN, int64_t strideC,
-                         int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count, int32_t r_begin, int32_t r_count,
-                         float* out_nc, void* stream) {
+namespace {
+int gm_geom(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN, int64_t strideC, int64_t strideH,
+            int64_t strideW, int32_t c_begin, int32_t c_count, int32_t r_begin, int32_t r_count, const float* out_nc, GmGeom* g) {
   const TensorView v = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, /*pad_front_if_odd=*/0);
   const TensorView r = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, r_begin, r_count, /*pad_front_if_odd=*/0);
   if (const int rc = validate(v, {out_nc}, Checks::Channels)) return rc;
   if (const int rc = validate(r, {out_nc}, Checks::Channels)) return rc;
   if (const int rc = validate(v, {out_nc}, Checks::All)) return rc;
   if (!v.dense_rows()) return DCTS_E_UNSUPPORTED;  // strideH > W
-  return dispatch_gm(GmGeom{x, N, strideN, strideC, c_begin, c_count, r_begin, r_count, (int)(H * W)}, out_nc,
-                     reinterpret_cast<hipStream_t>(stream));
+  *g = GmGeom{x, N, strideN, strideC, c_begin, c_count, r_begin, r_count, (int)(H * W)};
+  return DCTS_OK;
+}
+}  // namespace
+
+int dcts_gm_distance_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN, int64_t strideC,
+                         int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count, int32_t r_begin, int32_t r_count,
+                         float* out_nc, void* stream) {
+  GmGeom g;
+  if (const int rc = gm_geom(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, r_begin, r_count, out_nc, &g))
+    return rc;
+  return dispatch_gm(g, out_nc, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The normalised metrics: the workspace holds the (mu, s) pairs of the scored range, then those of the reference range.
+size_t dcts_gm_workspace_bytes(int32_t metric, int64_t N, int32_t c_count, int32_t r_count) {
+  if (metric != DCTS_GM_COSINE && metric != DCTS_GM_CORRELATION) return 0;
+  if (N <= 0 || c_count <= 0 || r_count <= 0) return 0;
+  return gm_stats_bytes(N, c_count) + gm_stats_bytes(N, r_count);
+}
+
+int dcts_gm_distance_metric_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN, int64_t strideC,
+                                int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count, int32_t r_begin,
+                                int32_t r_count, float* out_nc, void* stream, int32_t metric, void* workspace,
+                                size_t workspace_bytes) {
+  GmGeom g;
+  if (const int rc = gm_geom(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, r_begin, r_count, out_nc, &g))
+    return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (metric == DCTS_GM_L2) return dispatch_gm(g, out_nc, st);
+  if (metric != DCTS_GM_COSINE && metric != DCTS_GM_CORRELATION) return DCTS_E_UNSUPPORTED;
+  if (!workspace) return DCTS_E_WORKSPACE;
+  if (reinterpret_cast<uintptr_t>(workspace) & 15) return DCTS_E_ALIGN;
+  const size_t scored = gm_stats_bytes(N, c_count), need = scored + gm_stats_bytes(N, r_count);
+  if (workspace_bytes < need) return DCTS_E_WORKSPACE;
+  basis_forget_range(workspace, need);  // the pairs overwrite whatever basis tables lay there
+  char* ws = reinterpret_cast<char*>(workspace);
+  return dispatch_gm_metric(g, metric == DCTS_GM_CORRELATION, reinterpret_cast<float2*>(ws), reinterpret_cast<float2*>(ws + scored),
+                            out_nc, st);
 }
 
 // ---- fp16 / bf16 inputs (half.hip) -----------------------------------------------------------------------------------

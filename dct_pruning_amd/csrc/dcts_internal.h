@@ -193,6 +193,11 @@ struct GmGeom {
   int hw;
 };
 int dispatch_gm(const GmGeom& g, float* out, hipStream_t st);
+// The normalised metrics (dcts_gm_distance_metric_f32): the same sum over the unit maps (x - mu) * s. One (mu, s) pair per map
+// of the scored range at sa ([N][c_count]) and of the reference range at sb ([N][r_count]), each gm_stats_bytes() long, written
+// by a launch of their own in front of the distance kernel. center: mu is the map's mean (correlation), else 0 (cosine).
+inline size_t gm_stats_bytes(long long N, int count) { return align_up((size_t)N * (size_t)count * sizeof(float2), 256); }
+int dispatch_gm_metric(const GmGeom& g, bool center, float2* sa, float2* sb, float* out, hipStream_t st);
 
 // ---- half.hip: fp16 / bf16 inputs (dcts_energy_typed) -------------------------------------------------------------
 // MapGeom for 2-byte elements (raw bits; the dtype travels beside it). Rows are dense: strideH == W.

@@ -3,7 +3,11 @@
 // FPGM's rule for filter weights (prune what lies closest to the geometric median of its layer) applied to the maps a layer
 // produces: a map whose summed distance to the others is small is the one the others can replace. High = far = keep.
 //
-// The only kernel of the library that is all-pairs within a sample: compute-bound, LDS-tiled, fp32 VALU.
+// With a metric (dcts_gm_distance_metric_f32) the same sum runs over unit maps: x / |x| (cosine) or (x - mean) / |x - mean|
+// (correlation), so that a map and a scaled copy of it are at distance 0 and a large norm alone is not "far". k_gm_stats
+// leaves one (mu, s) pair per map in the caller's workspace, k_gm_distance<.., NORM = true> applies it where it stages a map.
+//
+// k_gm_distance is the only kernel of the library that is all-pairs within a sample: compute-bound, LDS-tiled, fp32 VALU.
 //
 //   k_gm_distance  one workgroup (kGmThreads = 256 = 16 x 16) owns one sample and a tile of kGmTS = 64 scored channels. It walks
 //                  the reference set in tiles of kGmTR = 64 channels, ascending from r_begin, and for every reference tile
@@ -19,7 +23,7 @@
 // elements, so d(a, a) = +0.0, d(a, b) has the bits of d(b, a), and near-duplicate maps - the pairs this criterion exists to
 // find - lose nothing to cancellation. A pair's chains depend on the two maps alone; a row's sum on the position of every
 // reference channel RELATIVE TO r_begin (tile = k / 64, lane = k % 16, j = k % 64 / 16) and on nothing else: not on N, c_begin,
-// c_count, the row's place in its tile or the launch. No atomics, no workspace, no second kernel.
+// c_count, the row's place in its tile or the launch. No atomics; without a metric no workspace and no second kernel.
 //
 // Tails in C and in H * W are zeros in LDS (a zero pair of elements adds fma(0, 0, acc) = acc); nothing is read from a clamped
 // address. LDS image: [channel][kGmLD = 68] floats per tile. A thread reads four consecutive elements of a channel
@@ -45,12 +49,20 @@ constexpr int TS = kGmTS, TR = kGmTR, KP = kGmKP, LD = kGmLD, THREADS = kGmThrea
 static_assert(TS == 64 && TR == 64 && THREADS == 256, "thread (ty, tx) of 16 x 16 owns rows ty + 16 i and columns tx + 16 j, i, j < 4");
 static_assert(KP % 4 == 0 && LD % 4 == 0 && (LD / 4) % 2 == 1 && LD >= KP, "16-byte rows, an odd number of 16-byte slots apart");
 
+// an element of a unit map from the element of the map and the map's (mu, s): see stage_tile
+__device__ __forceinline__ float unit(float x, float2 ms) { return __builtin_fmaf(x - ms.x, ms.y, 0.f); }
+
 // One tile's share of a chunk, global -> LDS: channels [ch0, ch0 + 64) of the range that starts at `base` (element 0 of its
 // channel 0 in this sample) and has `count` channels, elements [p0, p0 + KP). Out of range: zeros, and no load. Four loads are
 // in flight per thread before their stores.
-template <bool VEC>
+// NORM: what lands in LDS is the unit map, (x - mu) * s with the (mu, s) pair k_gm_stats left for the element's channel in
+// `stats` (pair 0: channel 0 of the range in this sample), fetched once per channel row of the call: a 16-byte-path thread holds
+// four rows, a dword-path wave one row at a time, so there the pair is wave-uniform and read as such. The product is rounded
+// once and +0.0 is added to it: a flat map (s = 0) becomes +0.0 in every element whatever the sign of x - mu, and no other
+// value changes. Out of range stays 0, not (0 - mu) * s, and no pair is read for a channel beyond the range.
+template <bool VEC, bool NORM>
 __device__ __forceinline__ void stage_tile(const float* __restrict__ base, long long strideC, int count, int ch0, int hw, int p0,
-                                           float* __restrict__ lds) {
+                                           float* __restrict__ lds, const float2* __restrict__ stats) {
   constexpr int PER = VEC ? KP / 4 : KP;     // threads per channel row
   constexpr int ROWS = THREADS / PER;        // channel rows per step
   constexpr int E = VEC ? 4 : 1;
@@ -62,10 +74,25 @@ __device__ __forceinline__ void stage_tile(const float* __restrict__ base, long 
   for (int i = 0; i < TS / ROWS; ++i) {
     const bool ok = inside && ch0 + c + ROWS * i < count;
     const float* s = src + (long long)(ROWS * i) * strideC;
-    if constexpr (VEC)
-      *reinterpret_cast<float4*>(dst + ROWS * i * LD) = ok ? *reinterpret_cast<const float4*>(s) : float4{0.f, 0.f, 0.f, 0.f};
-    else
-      dst[ROWS * i * LD] = ok ? *s : 0.f;
+    if constexpr (!NORM) {
+      if constexpr (VEC)
+        *reinterpret_cast<float4*>(dst + ROWS * i * LD) = ok ? *reinterpret_cast<const float4*>(s) : float4{0.f, 0.f, 0.f, 0.f};
+      else
+        dst[ROWS * i * LD] = ok ? *s : 0.f;
+    } else {
+      const int ch = ch0 + ROWS * i + (VEC ? c : __builtin_amdgcn_readfirstlane(c));  // PER == 64: a wave is one channel row
+      const float2 ms = ch < count ? stats[ch] : float2{0.f, 0.f};
+      if constexpr (VEC) {
+        float4 v{0.f, 0.f, 0.f, 0.f};
+        if (ok) {
+          const float4 t = *reinterpret_cast<const float4*>(s);
+          v = float4{unit(t.x, ms), unit(t.y, ms), unit(t.z, ms), unit(t.w, ms)};
+        }
+        *reinterpret_cast<float4*>(dst + ROWS * i * LD) = v;
+      } else {
+        dst[ROWS * i * LD] = ok ? unit(*s, ms) : 0.f;
+      }
+    }
   }
 }
 
@@ -78,8 +105,11 @@ __device__ __forceinline__ void pair_step(v2f a, v2f b, v2f& acc) {
   acc = __builtin_elementwise_fma(d, d, acc);
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(THREADS) void k_gm_distance(GmGeom g, float* __restrict__ out) {
+// NORM: the distance between the unit maps; sa / sb: the (mu, s) pairs of the scored and of the reference range, [N][c_count]
+// and [N][r_count] (k_gm_stats). Without NORM they are not read.
+template <bool VEC, bool NORM>
+__global__ __launch_bounds__(THREADS) void k_gm_distance(GmGeom g, float* __restrict__ out, const float2* __restrict__ sa,
+                                                         const float2* __restrict__ sb) {
   __shared__ __attribute__((aligned(16))) float sA[TS * LD];
   __shared__ __attribute__((aligned(16))) float sB[TR * LD];
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
@@ -90,6 +120,10 @@ __global__ __launch_bounds__(THREADS) void k_gm_distance(GmGeom g, float* __rest
   const float* abase = xs + (long long)g.c_begin * g.strideC;
   const float* bbase = xs + (long long)g.r_begin * g.strideC;
   const int hw = g.hw;
+  if constexpr (NORM) {
+    sa += n * g.c_count;
+    sb += n * g.r_count;
+  }
 
   float row[4] = {0.f, 0.f, 0.f, 0.f};
 
@@ -101,8 +135,8 @@ __global__ __launch_bounds__(THREADS) void k_gm_distance(GmGeom g, float* __rest
       for (int j = 0; j < 4; ++j) acc[i][j] = v2f{0.f, 0.f};
 
     for (int p0 = 0; p0 < hw; p0 += KP) {
-      stage_tile<VEC>(abase, g.strideC, g.c_count, s0, hw, p0, sA);
-      stage_tile<VEC>(bbase, g.strideC, g.r_count, r0, hw, p0, sB);
+      stage_tile<VEC, NORM>(abase, g.strideC, g.c_count, s0, hw, p0, sA, sa);
+      stage_tile<VEC, NORM>(bbase, g.strideC, g.r_count, r0, hw, p0, sB, sb);
       __syncthreads();
 #pragma unroll 2
       for (int q = 0; q < KP; q += 4) {
@@ -141,6 +175,77 @@ __global__ __launch_bounds__(THREADS) void k_gm_distance(GmGeom g, float* __rest
   }
 }
 
+// ---- the unit maps' (mu, s) pairs ----------------------------------------------------------------------------------------
+// One wave per map, kGmStatsMaps maps per workgroup, one workgroup per kGmStatsMaps maps and no grid loop. pairs[n * count + j] =
+// (mu, s) of channel begin + j of sample n:
+//   CENTER (correlation)  mu = sum / hw, s = 1 / sqrt(sum_p (x_p - mu)^2);  s = 0 for a flat map: max == min, an exact
+//                         comparison taken in the pass of the sum. No threshold on the centred sum: the rounding of mu alone
+//                         leaves a constant map a centred sum that is not 0, a unit vector of noise.
+//   otherwise (cosine)    mu = 0, s = 1 / sqrt(sum_p x_p^2);  s = 0 where that sum is 0.
+// Two passes, never sum x^2 - hw * mu^2, which cancels for the maps whose pattern is small against their mean; the second read
+// of a map comes from the cache its first read filled. (A centred sum that underflows to 0 gives s = 0 as well, not 1 / 0: maps
+// of denormal spread are outside the contract.)
+// The order of every sum is a function of p and hw alone: the elements in groups of four, group q = p / 4 to lane q % 64, q
+// ascending; a lane keeps one chain per position p % 4 in the group, adds them as (c0 + c1) + (c2 + c3), and a xor tree over
+// the 64 lanes (32, 16, ... 1) leaves the same bits in every lane. Elements beyond hw are skipped, not added as zeros. The
+// 16-byte path (a group is one load; hw is a multiple of 4 there) and the dword path feed the same chains: the same bits.
+template <bool VEC>
+__device__ __forceinline__ int load_group(const float* __restrict__ x, int q, int hw, float (&v)[4]) {
+  if constexpr (VEC) {
+    const float4 t = *reinterpret_cast<const float4*>(x + 4 * q);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+    return 4;
+  } else {
+    const int live = hw - 4 * q < 4 ? hw - 4 * q : 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = e < live ? x[4 * q + e] : 0.f;
+    return live;
+  }
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <bool VEC, bool CENTER>
+__global__ __launch_bounds__(kGmStatsThreads) void k_gm_stats(GmGeom g, int begin, int count, float2* __restrict__ pairs) {
+  const int lane = threadIdx.x & 63;
+  const long long m = (long long)blockIdx.x * kGmStatsMaps + (threadIdx.x >> 6);
+  if (m >= g.N * count) return;  // the whole wave
+  const long long n = m / count;
+  const float* x = g.x + n * g.strideN + (begin + (m - n * count)) * g.strideC;
+  const int hw = g.hw, groups = (hw + 3) >> 2;
+
+  float mu = 0.f;
+  bool flat = false;
+  if constexpr (CENTER) {
+    float c[4] = {0.f, 0.f, 0.f, 0.f}, lo = INFINITY, hi = -INFINITY;
+    for (int q = lane; q < groups; q += 64) {
+      float v[4];
+      const int live = load_group<VEC>(x, q, hw, v);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (e < live) c[e] += v[e], lo = fminf(lo, v[e]), hi = fmaxf(hi, v[e]);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) lo = fminf(lo, __shfl_xor(lo, off, 64)), hi = fmaxf(hi, __shfl_xor(hi, off, 64));
+    mu = wave_sum((c[0] + c[1]) + (c[2] + c[3])) / (float)hw;
+    flat = hi == lo;
+  }
+  float c[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int q = lane; q < groups; q += 64) {
+    float v[4];
+    const int live = load_group<VEC>(x, q, hw, v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e < live) c[e] = __builtin_fmaf(v[e] - mu, v[e] - mu, c[e]);
+  }
+  const float ss = wave_sum((c[0] + c[1]) + (c[2] + c[3]));
+  if (lane == 0) pairs[m] = float2{mu, (flat || ss == 0.f) ? 0.f : 1.0f / sqrtf(ss)};
+}
+
 }  // namespace
 
 namespace dctsi {
@@ -150,9 +255,36 @@ int dispatch_gm(const GmGeom& g, float* out, hipStream_t st) {
   if (blocks > kGmMaxBlocks) return DCTS_E_SHAPE;
   const bool vec = (reinterpret_cast<uintptr_t>(g.x) & 15) == 0 && g.strideN % 4 == 0 && g.strideC % 4 == 0 && g.hw % 4 == 0;
   if (vec)
-    hipLaunchKernelGGL(k_gm_distance<true>, dim3((unsigned)blocks), dim3(THREADS), 0, st, g, out);
+    hipLaunchKernelGGL((k_gm_distance<true, false>), dim3((unsigned)blocks), dim3(THREADS), 0, st, g, out, nullptr, nullptr);
   else
-    hipLaunchKernelGGL(k_gm_distance<false>, dim3((unsigned)blocks), dim3(THREADS), 0, st, g, out);
+    hipLaunchKernelGGL((k_gm_distance<false, false>), dim3((unsigned)blocks), dim3(THREADS), 0, st, g, out, nullptr, nullptr);
+  return (int)hipGetLastError();
+}
+
+// The (mu, s) pairs of both ranges, then the distances between the unit maps: two or three launches on `st`, all or none (both
+// grids are checked first). Where the scored range is the reference range its pairs are computed once, into sa.
+int dispatch_gm_metric(const GmGeom& g, bool center, float2* sa, float2* sb, float* out, hipStream_t st) {
+  const long long blocks = g.N * ((g.c_count + TS - 1) / TS);
+  const int larger = g.c_count > g.r_count ? g.c_count : g.r_count;
+  const long long stats_blocks = (g.N * larger + kGmStatsMaps - 1) / kGmStatsMaps;
+  if (blocks > kGmMaxBlocks || stats_blocks > kGmMaxBlocks) return DCTS_E_SHAPE;
+  const bool vec = (reinterpret_cast<uintptr_t>(g.x) & 15) == 0 && g.strideN % 4 == 0 && g.strideC % 4 == 0 && g.hw % 4 == 0;
+  auto stats = [&](int begin, int count, float2* pairs) {
+    const dim3 grid((unsigned)((g.N * count + kGmStatsMaps - 1) / kGmStatsMaps)), block(kGmStatsThreads);
+    const auto kernel = vec ? (center ? k_gm_stats<true, true> : k_gm_stats<true, false>)
+                            : (center ? k_gm_stats<false, true> : k_gm_stats<false, false>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, g, begin, count, pairs);
+    return (int)hipGetLastError();
+  };
+  if (const int rc = stats(g.c_begin, g.c_count, sa)) return rc;
+  if (g.r_begin == g.c_begin && g.r_count == g.c_count)
+    sb = sa;
+  else if (const int rc = stats(g.r_begin, g.r_count, sb))
+    return rc;
+  if (vec)
+    hipLaunchKernelGGL((k_gm_distance<true, true>), dim3((unsigned)blocks), dim3(THREADS), 0, st, g, out, sa, sb);
+  else
+    hipLaunchKernelGGL((k_gm_distance<false, true>), dim3((unsigned)blocks), dim3(THREADS), 0, st, g, out, sa, sb);
   return (int)hipGetLastError();
 }
 

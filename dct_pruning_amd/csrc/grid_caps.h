@@ -77,6 +77,10 @@ constexpr int kGmTR = 64;
 constexpr int kGmKP = 64;
 constexpr int kGmLD = kGmKP + 4;
 constexpr long long kGmMaxBlocks = 0x7fffffffLL;
+// gm.hip, k_gm_stats (the normalised metrics' pass over every map): one wave per map, workgroups of kGmStatsThreads threads
+// = kGmStatsMaps waves, one workgroup per kGmStatsMaps maps and no grid-stride loop either: the same largest grid, the same refusal
+constexpr int kGmStatsThreads = 256;
+constexpr int kGmStatsMaps = kGmStatsThreads / 64;
 
 // nhwc.hip: waves per workgroup of the lane = channel kernel (a wave takes 64 channels of one sample), and the channels a
 // workgroup of the block kernel (edges 14 ... 32) and of the strip kernel (edge 56) takes

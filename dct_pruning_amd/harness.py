@@ -41,7 +41,11 @@ Additions (opt-in, results identical on fixed batches):
                       "full" and "input" hooks, the last 12 for "last12"), high = far from the others = keep; the one
                       criterion that looks at a second channel. No odd pad (it changes no distance). Files go to
                       gm_score/<net>_limit<L>/gm_*.npy (hooks get_feature_hook_gm / get_feature_hook_densenet_gm /
-                      get_feature_hook_u2net_input_gm);
+                      get_feature_hook_u2net_input_gm). gm_metric="cosine" | "correlation" compares unit maps instead
+                      (x / |x|, or (x - mean) / |x - mean|: ops.gm_distance_nc(metric=...)), so that a channel's gain, which
+                      BatchNorm sets per channel, does not count as distance and a scaled copy of a map is a duplicate; flat
+                      (dead) maps land at the low end with the duplicates. Those files go to
+                      gm_score/<net>_limit<L>_<metric>/gm_*.npy;
   autocast="fp16" | "bf16"
                       the forward sweeps run under torch.autocast; the hooks hand the tensors to ops.energy_nc in
                       whatever dtype arrives (float16 / bfloat16 maps are scored natively, dcts_energy_typed; a tensor
@@ -80,6 +84,8 @@ AUTOCAST = {"fp16": torch.float16, "bf16": torch.bfloat16}
 # the band criterion's partition (K, kind): imp_score(criterion="bands", bands=...) sets it for its hooks
 _band_cfg = (4, "square")
 _band_weight_cache = {}
+# the gm criterion's metric: imp_score(criterion="gm", gm_metric=...) sets it for its hooks, on every call
+_gm_metric = "l2"
 
 
 def _band_weights(H, W, device):
@@ -114,8 +120,10 @@ def _score_entropy(x, c_begin, c_count, pad):
 
 def _score_gm(x, c_begin, c_count, pad, ref):
     """The summed distance to the maps of `ref` = (begin, count), the hook kind's whole channel set, whichever channel range
-    of it is scored here (no odd pad: zeros in front of both maps change no distance)."""
-    return _gm_nc(x, c_begin=c_begin, c_count=c_count, ref_begin=ref[0], ref_count=ref[1])
+    of it is scored here (no odd pad: zeros in front of both maps change no distance). The metric is named only where it is
+    not the default's: "l2" is the call it always was."""
+    kw = {} if _gm_metric == "l2" else {"metric": _gm_metric}
+    return _gm_nc(x, c_begin=c_begin, c_count=c_count, ref_begin=ref[0], ref_count=ref[1], **kw)
 
 
 # A criterion is its scorer above and its row here; everything below reads the row.
@@ -128,9 +136,11 @@ def _score_gm(x, c_begin, c_count, pad, ref):
 #   deferred, autocast, channels_last   the modes it supports; `excluded`: {net: why it is out of scope}
 #   cross         the score of a map depends on other channels: the scorer also takes ref=(begin, count), the channels of the
 #                 hook kind (_kind_slice), which stay whole when a hook point is scored in channel ranges
+#   metrics       the distances it can be taken under (gm_metric=...), the default first; another than the default adds
+#                 _<metric> to the output dir. () for a criterion that has no such choice
 Criterion = collections.namedtuple(
-    "Criterion", "name root prefix score what kinds pad banded cost deferred autocast channels_last excluded cross",
-    defaults=(("full", "last12", "input"), True, False, lambda H, W: H * W, False, False, False, {}, False))
+    "Criterion", "name root prefix score what kinds pad banded cost deferred autocast channels_last excluded cross metrics",
+    defaults=(("full", "last12", "input"), True, False, lambda H, W: H * W, False, False, False, {}, False, ()))
 _TABLE = {c.name: c for c in (
     Criterion("dct", "importance_score", None, _score_dct, "the DCT energy of every map",
               deferred=True, autocast=True, channels_last=True),
@@ -145,7 +155,7 @@ _TABLE = {c.name: c for c in (
     Criterion("entropy", "entropy_score", "ent_", _score_entropy, "the spectral entropy of every map"),
     Criterion("gm", "gm_score", "gm_", _score_gm,
               "the summed distance of every map to the maps of the hook's channels (the geometric-median criterion)",
-              pad=False, cross=True),
+              pad=False, cross=True, metrics=tuple(ops.GM_METRICS)),
 )}
 CRITERIA = tuple(_TABLE)
 
@@ -394,13 +404,18 @@ class _ChannelsLastLoader:
             yield data.contiguous(memory_format=torch.channels_last), target
 
 
-def check_options(criterion, net, deferred=False, autocast=None, channels_last=False, bands=(4, "square")):
+def check_options(criterion, net, deferred=False, autocast=None, channels_last=False, bands=(4, "square"), gm_metric="l2"):
     """Raises the ValueError of the first rule an imp_score call with these options breaks: what the criterion's row
     supports, and the two rules that hold for every criterion (autocast and channels_last have no deferred mode,
     channels_last does not cover u2netp). importance_generation.py's parser rejects its command lines with it."""
     if criterion not in CRITERIA:
         raise ValueError("imp_score: unknown criterion %r (expected one of %s)" % (criterion, ", ".join(CRITERIA)))
     crit = _TABLE[criterion]
+    if gm_metric != "l2" and gm_metric not in crit.metrics:
+        if crit.metrics:
+            raise ValueError("imp_score: gm_metric must be one of %s, got %r" % (", ".join(crit.metrics), gm_metric))
+        raise ValueError("imp_score: gm_metric=%r goes with criterion='gm' only (the %s criterion compares no maps)"
+                         % (gm_metric, criterion))
     if autocast is not None:
         if autocast not in AUTOCAST:
             raise ValueError("imp_score: autocast must be None, 'fp16' or 'bf16', got %r" % (autocast,))
@@ -429,20 +444,23 @@ def check_options(criterion, net, deferred=False, autocast=None, channels_last=F
 
 
 def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host", group=None, deferred=False,
-              criterion="dct", bands=(4, "square"), autocast=None, channels_last=False):
+              criterion="dct", bands=(4, "square"), autocast=None, channels_last=False, gm_metric="l2"):
     """Counterpart of utils/common.py:367-977. `args` needs .net, .limit (and whatever
     load_data reads when train_loader is None). criterion="rank" scores HRank's feature-map rank instead of the
     DCT energy and writes rank_conv/<net>_limit<L>/rank_*.npy. criterion="bands" with bands=(K, kind) writes the
     [C, K] band spectrum of every hook point to band_score/<net>_limit<L>_<kind><K>/band_*.npy. criterion="entropy"
     scores the spectral entropy of every map's DCT coefficients and writes entropy_score/<net>_limit<L>/ent_*.npy (all
     seven nets; not with deferred, autocast or channels_last). criterion="gm" scores every map's summed distance to the
-    maps of its hook's channels and writes gm_score/<net>_limit<L>/gm_*.npy (all seven nets; same exclusions).
+    maps of its hook's channels and writes gm_score/<net>_limit<L>/gm_*.npy (all seven nets; same exclusions); with
+    gm_metric="cosine" / "correlation" the distance is taken between unit maps and the files go to
+    gm_score/<net>_limit<L>_<metric>/ (criterion "gm" only).
     autocast="fp16" / "bf16" runs the forward sweeps under torch.autocast and scores the half-precision tensors the
     hooks then see as they are (criterion "dct" only, not with deferred).
     channels_last=True converts the net (in place) and every input batch to torch.channels_last; the tensors the hooks
     then see are scored in the layout they arrive in (criterion "dct" only, not with deferred, not u2netp)."""
-    global _acc, _band_cfg
-    check_options(criterion, args.net, deferred, autocast, channels_last, bands)
+    global _acc, _band_cfg, _gm_metric
+    check_options(criterion, args.net, deferred, autocast, channels_last, bands, gm_metric)
+    _gm_metric = gm_metric
     crit = _TABLE[criterion]
     if not hasattr(args, "limit"):
         # utils/load_models.py:819 calls imp_score from prune_*.py whose parsers define no --limit
@@ -455,6 +473,8 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
         _band_cfg = (int(bands[0]), bands[1])
         width = _band_cfg[0]
         out_dir += "_%s%d" % (_band_cfg[1], width)
+    if gm_metric != "l2":
+        out_dir += "_" + gm_metric
     world, rank = 1, 0
     if group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
         world = torch.distributed.get_world_size(group)

@@ -350,7 +350,10 @@ def rank_nc(x, c_begin=0, c_count=None, out=None):
     return out
 
 
-def gm_distance_nc(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, out=None):
+GM_METRICS = {"l2": 0, "cosine": 1, "correlation": 2}  # DCTS_GM_*
+
+
+def gm_distance_nc(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, out=None, metric="l2"):
     """G[n, j] = sum_k ||x[n, c_begin+j] - x[n, k]||_2 over the reference channels k in [ref_begin, ref_begin + ref_count)
     -> [N, c_count] fp32 (ref_count None = to the end).
 
@@ -359,11 +362,23 @@ def gm_distance_nc(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, out=
     stand in for, scores low; high = keep. Computed in the difference form: the term of a map with itself is exactly 0, two
     identical maps are at distance +0.0, and pieces of a channel range scored against the same reference set concatenate
     to the unsplit result bit for bit. There is no odd front pad: zeros in front of both maps change no distance.
+    metric: "l2" compares the maps as they are. "cosine" and "correlation" (dcts_gm_distance_metric_f32) compare unit maps,
+    x / ||x|| and (x - mean) / ||x - mean||, so that a map and a scaled copy of it are at distance 0 (exactly +0.0 for a power of
+    two) and every term lies in [0, 2]. A map with nothing to normalise (all zeros; under "correlation" any constant map) counts
+    as the zero map: distance 1 to every other map, exactly 0 to the other flat ones, so dead channels score low.
     float32 NCHW only; a tensor whose maps are not dense (stride(3) != 1 or stride(2) != W) is copied with .contiguous()
     first. Enqueues on the current stream of x's device; no synchronisation."""
+    if metric not in GM_METRICS:
+        raise ValueError("metric must be one of %s, got %r" % (", ".join(GM_METRICS), metric))
     x, c_begin, c_count, out, stream = _open(x, c_begin, c_count, out, rows="dense")
     ref_begin, ref_count = _slice(x, ref_begin, ref_count)
     N, C, H, W = x.shape
-    _launch(x.device, _lib.load().dcts_gm_distance_f32, x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
-            c_begin, c_count, ref_begin, ref_count, out.data_ptr(), stream)
+    lib = _lib.load()
+    args = (x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3), c_begin, c_count, ref_begin, ref_count,
+            out.data_ptr(), stream)
+    if metric == "l2":
+        _launch(x.device, lib.dcts_gm_distance_f32, *args)
+        return out
+    ws = _workspace(x.device, stream, max(lib.dcts_gm_workspace_bytes(GM_METRICS[metric], N, c_count, ref_count), 16))
+    _launch(x.device, lib.dcts_gm_distance_metric_f32, *args, GM_METRICS[metric], ws.data_ptr(), ws.numel())
     return out

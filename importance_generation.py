@@ -11,7 +11,8 @@ Extra, opt-in flags: --synthetic (seeded synthetic batches; also lifts the need 
 the DCT energy under importance_score/, HRank's feature-map rank under rank_conv/, the DCT energy of K frequency bands
 per channel, --bands K --band_kind {square,diag}, under band_score/, the spectral entropy of the DCT coefficients
 under entropy_score/, or every map's summed distance to the other maps of its layer, the geometric-median criterion, under
-gm_score/), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
+gm_score/; --gm_metric {l2,cosine,correlation} takes that distance between the maps as they are or between unit maps, which
+go to gm_score/<net>_limit<L>_<metric>/), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
 half-precision feature maps are scored as they are) and --channels_last (the net and its inputs run in
 torch.channels_last and the feature maps are scored in the layout they arrive in). dct_pruning_amd/harness.py says
 what each criterion writes and which of these modes and nets it supports (its criterion table and check_options, which
@@ -55,6 +56,10 @@ def parse_args(argv=None):
     parser.add_argument("--bands", type=int, default=4, help="--criterion bands: number of bands K, 1 ... %d" % bands.BAND_MAX)
     parser.add_argument("--band_kind", type=str, default="square", choices=("square", "diag"),
                         help="--criterion bands: L-infinity shells (square) or anti-diagonal stripes (diag)")
+    parser.add_argument("--gm_metric", type=str, default="l2", choices=harness._TABLE["gm"].metrics,
+                        help="--criterion gm: l2 compares the maps as they are; cosine (x / |x|) and correlation "
+                             "((x - mean) / |x - mean|) compare unit maps, so a channel's gain is no distance and a scaled "
+                             "copy is a duplicate (gm_score/<net>_limit<L>_<metric>/)")
     parser.add_argument("--autocast", type=str, default=None, choices=("fp16", "bf16"),
                         help="run the forward sweeps under torch.autocast and score the half-precision feature maps natively")
     parser.add_argument("--channels_last", action="store_true",
@@ -62,7 +67,7 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     try:
         harness.check_options(args.criterion, args.net, args.deferred, args.autocast, args.channels_last,
-                              (args.bands, args.band_kind))
+                              (args.bands, args.band_kind), gm_metric=args.gm_metric)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -118,7 +123,7 @@ def main(argv=None):
     harness.imp_score(net, args, single_sweep=args.single_sweep,
                       accumulate="device" if args.device_accumulate else "host", deferred=args.deferred,
                       criterion=args.criterion, bands=(args.bands, args.band_kind), autocast=args.autocast,
-                      channels_last=args.channels_last)
+                      channels_last=args.channels_last, gm_metric=args.gm_metric)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -49,7 +49,8 @@ extern "C" {
  *    (dcts_energy_typed, dcts_typed_workspace_bytes, dcts_has_half_kernel, DCTS_DTYPE_*) and for the channels-last ones
  *    (dcts_energy_nhwc, dcts_nhwc_workspace_bytes, dcts_has_nhwc_kernel), and for the spectral-entropy ones
  *    (dcts_spectral_entropy_f32, dcts_entropy_workspace_bytes, dcts_has_entropy_kernel), and for the geometric-median
- *    criterion's entry point (dcts_gm_distance_f32). */
+ *    criterion's entry point (dcts_gm_distance_f32) and its normalised metrics (dcts_gm_distance_metric_f32,
+ *    dcts_gm_workspace_bytes, DCTS_GM_*). */
 #define DCTS_ABI_VERSION 3
 
 enum {
@@ -282,6 +283,47 @@ int dcts_gm_distance_f32(const float* x, int64_t N, int64_t C_total, int64_t H, 
                          int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
                          int32_t c_begin, int32_t c_count, int32_t r_begin, int32_t r_count,
                          float* out_nc, void* stream);
+
+/*
+ * dcts_gm_distance_f32 under another metric: the same sum over UNIT maps, so that the pattern of a map is compared and not its
+ * gain (the plain distance obeys ||a - b|| >= | ||a|| - ||b|| |: a map with a large norm is far from everything).
+ *
+ *     out_nc[n*c_count + j] = sum_{k = r_begin}^{r_begin+r_count-1} || u[n, c_begin+j] - u[n, k] ||_2,   every term in [0, 2]
+ *
+ *   DCTS_GM_L2           u = x: dcts_gm_distance_f32 itself, bit for bit; no workspace (NULL / 0 are fine).
+ *   DCTS_GM_COSINE       u = x / ||x||_2                        d^2 = 2 - 2 cos(a, b)
+ *   DCTS_GM_CORRELATION  u = (x - mu) / ||x - mu||_2, mu the mean of the map    d^2 = 2 - 2 rho (Pearson)
+ *   Flat maps: a map with nothing to normalise has u = 0, every element exactly +0.0. For the cosine that is a map with
+ *              sum x^2 == 0; for the correlation a map whose maximum equals its minimum (an exact comparison, no threshold on
+ *              the centred sum). A flat map is at distance 1 (to rounding) from every map that is not flat and at exactly 0 from
+ *              every other flat map: dead channels score low, next to the duplicates. High = far = keep, as ever.
+ *   metric     any other value: DCTS_E_UNSUPPORTED.
+ *   workspace  device memory, 16-byte aligned, at least dcts_gm_workspace_bytes(metric, N, c_count, r_count) bytes (0 for
+ *              DCTS_GM_L2): one (mu, 1 / norm) pair per scored and per reference map, written by a launch of their own before the
+ *              distances. The call overwrites it; a workspace shared with the other entry points is handled as theirs
+ *              (dcts_workspace_invalidate[_range] for memory that is freed or written by the caller).
+ *   Checks, in this order: everything dcts_gm_distance_f32 checks, in its order; the metric; the workspace (NULL or too small:
+ *              DCTS_E_WORKSPACE; not 16-byte aligned: DCTS_E_ALIGN). A call that needs more than
+ *              2^31 - 1 workgroups in either launch (4 maps or 64 scored channels of a sample each) returns DCTS_E_SHAPE.
+ * Arithmetic, all fp32: mu = sum / (H*W); the norm from a SECOND pass over the map, sum (x - mu)^2, never sum x^2 - H*W*mu^2;
+ * every sum in an order that depends on the element's index and on H*W alone. u = (x - mu) * (1 / norm), rounded once. Then the
+ * difference form of dcts_gm_distance_f32, with what it makes exact: the k == c term, identical maps, d(a, b) against d(b, a).
+ * New: a map and a power-of-two multiple of it are at distance exactly +0.0 (sum (2^k x)^2 = 4^k sum x^2, and the correctly
+ * rounded square root and division commute with that scaling), for every k that makes nothing denormal or overflow.
+ * Everything dcts_gm_distance_f32 says about independence holds: out[n, j] does not depend on N, c_begin / c_count, the launch
+ * or the alignment of x. A NaN map poisons its own sample only.
+ * Limit: the centring is done in fp32. A map that is nearly constant without being flat (spread within a few ulp of its
+ * mean) has a unit map that is mostly rounding; the criterion is not meaningful there, and the tests hold no such map.
+ * Only enqueues on `stream`: no allocation, no atomics; the arguments are checked before any launch.
+ */
+#define DCTS_GM_L2 0
+#define DCTS_GM_COSINE 1
+#define DCTS_GM_CORRELATION 2
+size_t dcts_gm_workspace_bytes(int32_t metric, int64_t N, int32_t c_count, int32_t r_count);
+int dcts_gm_distance_metric_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                                int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
+                                int32_t c_begin, int32_t c_count, int32_t r_begin, int32_t r_count,
+                                float* out_nc, void* stream, int32_t metric, void* workspace, size_t workspace_bytes);
 
 /*
  * dcts_energy_f32 for feature maps of another element type: what a forward pass under autocast hands to a hook.

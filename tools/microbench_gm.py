@@ -9,7 +9,9 @@ pair_elems = N * C * C * H * W element pairs per call; each costs two fp32 VALU 
 subtract and a fused multiply-add): valu_ops = 2 * pair_elems. Reported: pair elements per second, and valu_ops per second
 as a share of the 157.3e12 of the MI355X's fp32 vector peak. That peak counts a packed fma as four operations (two lanes'
 multiply and add): one operation (a subtract or an fma) per lane and clock is 39.3e12 per second at 2.4 GHz, a share of 0.25.
-usage: tools/microbench_gm.py [--reps R] [N,C,H,W ...]"""
+--metric cosine | correlation times the normalised call (dcts_gm_distance_metric_f32): the stats launch that reads every map
+twice and the distance kernel that stages unit maps; pair_elems and the shares count the distance kernel's arithmetic alone.
+usage: tools/microbench_gm.py [--reps R] [--metric M] [N,C,H,W ...]"""
 import argparse
 import json
 import os
@@ -25,18 +27,18 @@ PEAK_FP32_VECTOR = 157.3e12
 WARMUP = 2
 
 
-def run(shape, reps):
+def run(shape, reps, metric):
     n, c, h, w = shape
     x = torch.relu(torch.randn(n, c, h, w, device="cuda"))
     out = torch.empty(n, c, device="cuda")
     for _ in range(WARMUP):
-        dpa.gm_distance_nc(x, out=out)
+        dpa.gm_distance_nc(x, out=out, metric=metric)
     torch.cuda.synchronize()
     pairs = []
     for _ in range(reps):
         a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        dpa.gm_distance_nc(x, out=out)
+        dpa.gm_distance_nc(x, out=out, metric=metric)
         z.record()
         pairs.append((a, z))
     torch.cuda.synchronize()
@@ -44,7 +46,7 @@ def run(shape, reps):
     med = ts[len(ts) // 2]
     pair_elems = n * c * c * h * w
     workgroups = n * -(-c // 64)
-    res = {"shape": list(shape), "reps": reps, "workgroups": workgroups, "median_ms": round(med, 3), "min_ms": round(ts[0], 3),
+    res = {"shape": list(shape), "metric": metric, "reps": reps, "workgroups": workgroups, "median_ms": round(med, 3), "min_ms": round(ts[0], 3),
            "max_ms": round(ts[-1], 3), "pair_elems": pair_elems, "pair_elems_per_s": round(pair_elems / med * 1e3, 1),
            "valu_ops_per_s": round(2 * pair_elems / med * 1e3, 1),
            "share_of_fp32_vector_peak": round(2 * pair_elems / med * 1e3 / PEAK_FP32_VECTOR, 4),
@@ -55,7 +57,8 @@ def run(shape, reps):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=21)
+    ap.add_argument("--metric", default="l2", choices=("l2", "cosine", "correlation"))
     ap.add_argument("shapes", nargs="*")
     a = ap.parse_args()
     for s in [tuple(int(v) for v in s.split(",")) for s in a.shapes] or SHAPES:
-        run(s, a.reps)
+        run(s, a.reps, a.metric)
