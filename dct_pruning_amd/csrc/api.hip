@@ -217,19 +217,7 @@ Choice choose(const TensorView& v, int algo, bool store, bool aligned16) {
 }
 
 // one tensor as a batch of one
-TileBatch single_batch(const TensorView& v, float* out) {
-  TileBatch tb;
-  for (int i = 0; i < kTileItems; ++i) {
-    tb.x[i] = v.base();
-    tb.out[i] = out;
-    tb.begin[i] = 0;
-  }
-  tb.begin[1] = tb.begin[kTileItems] = v.nmaps();
-  tb.map_elems = v.strideC;
-  tb.total = v.nmaps();
-  tb.count = 1;
-  return tb;
-}
+TileBatch single_batch(const TensorView& v, float* out) { return single_tensor_batch(v.base(), out, v.nmaps(), v.strideC); }
 
 // The direct kernel's basis tables live at the head of the caller's workspace. They are built once per
 // (workspace, stream, H', W') and reused by later calls: the library remembers - on the host, nothing is read

@@ -78,6 +78,21 @@ struct TileBatch {
   int count;
 };
 
+// one dense tensor of `nmaps` maps as a batch of one (every slot names it: a lookup never leaves the tensor)
+inline TileBatch single_tensor_batch(const float* x, float* out, long long nmaps, long long map_elems) {
+  TileBatch tb;
+  for (int i = 0; i < kTileItems; ++i) {
+    tb.x[i] = x;
+    tb.out[i] = out;
+    tb.begin[i] = 0;
+  }
+  tb.begin[1] = tb.begin[kTileItems] = nmaps;
+  tb.map_elems = map_elems;
+  tb.total = nmaps;
+  tb.count = 1;
+  return tb;
+}
+
 // compute units of the current device, queried once (256 on MI355X; the persistent grids are sized by it)
 inline int num_cus() {
   static const int n = [] {

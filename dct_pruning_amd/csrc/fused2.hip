@@ -75,7 +75,7 @@ __device__ __forceinline__ void fused2_body(const TileBatch& tb, lds_ptr buf0, l
   };
   auto lane_voff = [&](int strip) DCTS_LAMBDA_INLINE {
     const int lane = launder(lane_in);
-    return (strip * SW + lane < N) ? lane * 4 : kF2Out;
+    return (strip * SW + lane < N) ? lane * 4 : kLaneOut;
   };
   if (m < nmaps) {
     const float* first = tile_in(tb, m);
@@ -259,16 +259,25 @@ int launch_fused2(const TileBatch& tb, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+template <int M, int L>
+int coeff_fused2(const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps, hipStream_t st) {
+  auto launch = [st](const TileBatch& tb, float* leaf) {
+    const long long grid = tb.total < num_cus() ? tb.total : num_cus();
+    hipLaunchKernelGGL((k_split_fused2_coeff<M, L>), dim3((unsigned)grid), dim3(64 * Fused2Cfg<M, L>::NW), 0, st, tb, leaf);
+    return (int)hipGetLastError();
+  };
+  return run_coeff_chunks(launch, launch_assemble<M, L, true>, M << L, x, nmaps, out, scratch, scratch_maps, st);
+}
+
 }  // namespace
 
 namespace dctsi {
 
 int dispatch_fused2_coeff(int N, const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps,
                           hipStream_t st) {
-#define DCTS_CASE(N_, M_, L_)                                                                                      \
-  case N_:                                                                                                         \
-    return run_coeff_chunks(k_split_fused2_coeff<M_, L_>, launch_assemble<M_, L_, true>, N_,                       \
-                            64 * Fused2Cfg<M_, L_>::NW, x, nmaps, out, scratch, scratch_maps, st);
+#define DCTS_CASE(N_, M_, L_) \
+  case N_:                    \
+    return coeff_fused2<M_, L_>(x, nmaps, out, scratch, scratch_maps, st);
   switch (N) {
     DCTS_FUSED2_TABLE(DCTS_CASE)
     default:

@@ -23,6 +23,7 @@
 #include "../../include/dctscore.h"
 #include "codelet_sizes.h"
 #include "dct_codelets.hpp"
+#include "dcts_internal.h"  // num_cus
 
 #include "grid_caps.h"
 #include "rect.h"
@@ -177,16 +178,6 @@ __global__ __launch_bounds__(64 * kRectWaves) void k_energy_rect(RectGeom g, flo
   }
 }
 
-int rect_num_cus() {
-  static int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    return cus;
-  }();
-  return n;
-}
-
 bool rect_tab_1d(int n) {
 #define DCTS_CASE(N) \
   if (n == N) return true;
@@ -227,7 +218,7 @@ int dispatch_rect(const RectGeom& g_in, float* out, int store_coeff, hipStream_t
   const size_t lds = (size_t)kRectWaves * g.G * g.map_lds * sizeof(float);
   const long long ngroups = (g.nmaps + g.G - 1) / g.G;
   long long blocks = (ngroups + kRectWaves - 1) / kRectWaves;
-  const long long cap = (long long)rect_num_cus() * kRectBlocksPerCu;  // a grid several times the residency (codelet.hip, GRID_WAVES_PER_CU)
+  const long long cap = (long long)num_cus() * kRectBlocksPerCu;  // a grid several times the residency (codelet.hip, GRID_WAVES_PER_CU)
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   static const hipError_t attr_rc = [] {  // four 64 x 65 slabs are 66.6 KB: above the 64 KB a kernel gets without asking

@@ -1,6 +1,6 @@
 // split_common.hpp - what the split, fused, two-roles and pipelined kernels (split_kernels.hpp, fused.hip, fused2.hip,
 // pipe.hip) share on top of split_roles.hpp: the role butterflies on an LDS image, the role codelet, pass 1 on samples
-// loaded into registers, the deferred workgroup sum, the chunked coefficient launch and the stamp diagnostic.
+// loaded into registers, the deferred workgroup sum and the stamp diagnostic.
 // See split_kernels.hpp for the role tree these pieces implement.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -172,15 +172,7 @@ constexpr int fused_waves_per_simd() {
 // output). One __device__ symbol, read back by dcts_debug_fused_stamps (api.hip): all families in one unit (all_units.hip).
 #ifdef DCTS_FUSED_STAMPS
 __device__ unsigned long long g_fused_stamps[16][16];
-#define DCTS_STAMP(slot)                                                          \
-  do {                                                                            \
-    unsigned long long t_;                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");  \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    acc_[slot] += t_ - last_;                                                     \
-    last_ = t_;                                                                   \
-  } while (0)
+#define DCTS_STAMP(slot) DCTS_STAMP_BODY(slot)
 #else
 #define DCTS_STAMP(slot) ((void)0)
 #endif
@@ -211,7 +203,6 @@ __device__ __forceinline__ void fused_finish(lds_ptr partials, int slot, long lo
 // Same box, % of the HBM peak, staged -> register loads -> + pass-2 rounds alternating between the two buffers (two barriers
 // per round instead of three): 288 x 288: 28.7 -> 30.4 -> 31.2 (2048 maps), 30.8 -> 33.0 -> 34.2 (4999), 27.3 -> 28.9 -> 29.5 (768);
 // 320 x 320: 29.7 -> 31.0 -> 31.5 (2048). 219 / 248 VGPRs, no scratch.
-constexpr int kF2Out = 0x7ffffff0;  // a lane offset beyond any map: the load returns 0 and makes no request
 template <int M, int L, int P, int STRIP>
 __device__ __forceinline__ void f2_load_item(__amdgpu_buffer_rsrc_t rs, int voff, float (&y)[1 << L]) {
   constexpr int S = 1 << L, N = M << L;
@@ -249,32 +240,6 @@ __device__ __forceinline__ void f2_network_store(float (&y)[1 << L], lds_ptr ima
       colp[row * rs_lds] = y[s];
     });
   }
-}
-
-template <class Kernel, class Assemble>
-int run_coeff_chunks(Kernel kernel, Assemble assemble, int N, int threads, const float* x, long long nmaps, float* out,
-                     float* scratch, long long scratch_maps, hipStream_t st) {
-  if (!scratch || scratch_maps < 1) return DCTS_E_WORKSPACE;
-  for (long long m0 = 0; m0 < nmaps; m0 += scratch_maps) {
-    const long long nb = (nmaps - m0) < scratch_maps ? (nmaps - m0) : scratch_maps;
-    TileBatch tb;
-    for (int i = 0; i < kTileItems; ++i) {
-      tb.x[i] = x + m0 * (long long)N * N;
-      tb.out[i] = nullptr;  // the coefficient instantiations write no energies
-      tb.begin[i] = 0;
-    }
-    tb.begin[1] = tb.begin[kTileItems] = nb;
-    tb.map_elems = (long long)N * N;
-    tb.total = nb;
-    tb.count = 1;
-    const long long grid = nb < dctsi::num_cus() ? nb : dctsi::num_cus();
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), 0, st, tb, scratch);
-    int rc = (int)hipGetLastError();
-    if (rc) return rc;
-    rc = assemble(scratch, nb, out + m0 * (long long)N * N, st);
-    if (rc) return rc;
-  }
-  return DCTS_OK;
 }
 
 }  // namespace

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <utility>
+#include "../../include/dctscore.h"
 #include "dct_codelets.hpp"
 #include "dcts_internal.h"
 
@@ -207,6 +208,23 @@ __device__ __forceinline__ int launder(int v) {
   return v;
 }
 
+// A lane offset of a buffer load beyond any map: the hardware returns 0 and makes no request (lanes without an item, loads
+// behind the last map of a workgroup).
+constexpr int kLaneOut = 0x7ffffff0;
+
+// Diagnostic builds only (-DDCTS_FUSED_STAMPS, -DDCTS_T2_STAMPS, -DDCTS_G2_STAMPS): one s_memtime stamp at a phase boundary,
+// added to slot `slot` of the wave's acc_[16] (the body declares acc_ and last_; its family's __device__ array takes the sums
+// at the end). DCTS_STAMP, T2_STAMP and G2_STAMP are this or ((void)0), each under its family's switch.
+#define DCTS_STAMP_BODY(slot)                                                     \
+  do {                                                                            \
+    unsigned long long t_;                                                        \
+    __builtin_amdgcn_sched_barrier(0);                                            \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");  \
+    __builtin_amdgcn_sched_barrier(0);                                            \
+    acc_[slot] += t_ - last_;                                                     \
+    last_ = t_;                                                                   \
+  } while (0)
+
 // wave64 sum by DPP within rows of 16 lanes, then the four row totals in fixed order: no index
 // registers (ds_bpermute needs one per offset), result uniform across the wave
 __device__ __forceinline__ float wave_sum_dpp(float v) {
@@ -315,6 +333,24 @@ inline int launch_assemble(const float* leaf, long long nmaps, float* out, hipSt
   if (blocks > 65536) blocks = 65536;
   hipLaunchKernelGGL((k_assemble<M, L, WEIGHTED>), dim3((unsigned)blocks), dim3(256), 0, st, leaf, nmaps, out);
   return (int)hipGetLastError();
+}
+
+// Coefficient output of `nmaps` dense N x N tiles through a large-tile kernel: the maps go through `scratch` (scratch_maps
+// tiles) in chunks. `launch(tb, scratch) -> int` runs the family's STORE kernel on one chunk - it owns its grid - and
+// `assemble` turns the chunk's leaf outputs into coefficients.
+template <class Launch, class Assemble>
+int run_coeff_chunks(Launch launch, Assemble assemble, int N, const float* x, long long nmaps, float* out, float* scratch,
+                     long long scratch_maps, hipStream_t st) {
+  if (!scratch || scratch_maps < 1) return DCTS_E_WORKSPACE;
+  for (long long m0 = 0; m0 < nmaps; m0 += scratch_maps) {
+    const long long nb = (nmaps - m0) < scratch_maps ? (nmaps - m0) : scratch_maps;
+    // (no energy output: the STORE instantiations write none)
+    int rc = launch(dctsi::single_tensor_batch(x + m0 * (long long)N * N, nullptr, nb, (long long)N * N), scratch);
+    if (rc) return rc;
+    rc = assemble(scratch, nb, out + m0 * (long long)N * N, st);
+    if (rc) return rc;
+  }
+  return DCTS_OK;
 }
 
 }  // namespace

@@ -38,17 +38,22 @@
 
 #include "../../include/dctscore.h"
 #include "dcts_internal.h"  // dispatch_tile2d, dispatch_tile2d_coeff
-#include "split_roles.hpp"
+#include "tile2_common.hpp"
+
+// tuning switches (tools/t2_dev.py): column slots of the next map that land in LDS, and its loads per hook point (T2Cfg)
+#ifndef DCTS_T2_DMACOLS
+#define DCTS_T2_DMACOLS 2
+#endif
+#ifndef DCTS_T2_HOOKS
+#define DCTS_T2_HOOKS 4, 4, 4, 12, 12, 12
+#endif
 
 namespace {
 
-// Instruction-mix replay (tools/t2_dev.py on a -DDCTS_T2_EXP=3 build): the product kernel with every
-// instruction in place but NO memory traffic - the loads of the next map read a zero-length buffer (the hardware
-// returns 0 without a request) and the direct-to-LDS pieces are not issued. What it measures is the ceiling of the
-// CU-side work of this design: cycles per map at 16 waves if HBM cost nothing (results are wrong by construction).
-#ifndef DCTS_T2_EXP
-#define DCTS_T2_EXP 0
-#endif
+// (An instruction-mix replay was measured on this kernel: every instruction in place but NO memory traffic - the next
+// map's loads read a zero-length buffer, the direct-to-LDS pieces are not issued - gave 0.53 of the HBM peak against the
+// product's 0.43-0.44: the ceiling of the CU-side work of this design at 16 waves. The switch gave wrong results by
+// construction and was removed; in history, profiles/r03_tile2d_replay_224.txt.)
 constexpr int kT2L = 3, kT2S = 8, kT2Waves = 16;
 constexpr RolePlan<kT2L> kT2Plan{};
 
@@ -104,17 +109,13 @@ constexpr T2Sched kT2Sch{};
 // The item slots (a, b) whose outputs belong to `set`, ordered by column slot b then a: slot i of
 // the set as a * S + b. A slot's register is free for the next map's sample once the set has been
 // written to LDS, so the next map is loaded set by set, eight slots per hook point.
+// (a-major instead of b-major order was measured equal and removed; in history.)
 constexpr int t2_set_slot(int set, int i, int bmax) {
   int role_of_slot[kT2S] = {};
   for (int r = 0; r < kT2S; ++r) role_of_slot[kT2Plan.slot_of_role[r]] = r;
   int n = 0;
-#ifdef DCTS_T2_AMAJOR
-  for (int a = 0; a < kT2S; ++a)
-    for (int b = 0; b < bmax; ++b)
-#else
   for (int b = 0; b < bmax; ++b)
     for (int a = 0; a < kT2S; ++a)
-#endif
       if (kT2Sch.set_of[role_of_slot[a] * kT2S + role_of_slot[b]] == set) {
         if (n == i) return a * kT2S + b;
         ++n;
@@ -155,13 +156,7 @@ struct T2Cfg {
   static constexpr int PI = 64 / M;                   // item rows per producer wave (2)
   static constexpr int PWAVES = (M + PI - 1) / PI;    // producer waves (14 for M = 28)
   static_assert(PWAVES <= NW, "producers");
-  static constexpr int NROT = 3;                      // rotations of the L = 3 network
-#ifndef DCTS_T2_DMACOLS
-#define DCTS_T2_DMACOLS 2
-#endif
-#ifndef DCTS_T2_HOOKS
-#define DCTS_T2_HOOKS 4, 4, 4, 12, 12, 12
-#endif
+  static constexpr int NROT = kT2Plan.nrot;           // rotations of the L = 3 network (3)
   // The last DB column slots of the NEXT map do not land in registers but in LDS (direct-to-LDS
   // loads into the 56 KB the Z set leaves free: no VGPRs, nothing for the register allocator to
   // spill), issued while set 0 is transformed; phase A reads them from there.
@@ -184,25 +179,6 @@ struct T2Cfg {
   // (a slot must not be loaded before its set has gone to LDS: checked where the hooks are built)
 };
 
-// rotation constants (c, s, sigma*c, sigma*s), sigma = (-1)^j of the pair index: [rot][p][4]
-template <int M>
-struct T2RotTable {
-  float v[T2Cfg<M>::NROT][M][4] = {};
-  constexpr T2RotTable() {
-    constexpr RotTable<M, kT2L> t{};
-    for (int r = 0; r < T2Cfg<M>::NROT; ++r)
-      for (int p = 0; p < M; ++p) {
-        const float sg = RotTable<M, kT2L>::sign0(r) * ((p & 1) ? -1.f : 1.f);
-        v[r][p][0] = t.c[r][p];
-        v[r][p][1] = t.s[r][p];
-        v[r][p][2] = sg * t.c[r][p];
-        v[r][p][3] = sg * t.s[r][p];
-      }
-  }
-};
-template <int M>
-__device__ const T2RotTable<M> kT2Rot{};
-
 // per (set, li): leaf types and squared amplitude weights of the block
 struct T2BlockParam {
   int tA, tB;                    // 1: DCT-IV along p' (A) / q' (B)
@@ -214,19 +190,12 @@ template <int M>
 struct T2ParamTable {
   T2BlockParam v[2][kT2S * kT2S / 2] = {};
 };
-template <int M, int R>
-constexpr void t2_role_weights(float& w0, float& w1) {
-  using Leaf = typename RoleLeaf<M * kT2S, kT2L, R>::type;
-  const double a = Leaf::wt(true), b = Leaf::wt(false);
-  w0 = float(a * a);
-  w1 = float(b * b);
-}
 template <int M, int... R>
 constexpr T2ParamTable<M> t2_make_params(std::integer_sequence<int, R...>) {
   constexpr RolePlan<kT2L> plan{};
   constexpr T2Sched sch{};
   float w0[kT2S] = {}, w1[kT2S] = {};
-  (t2_role_weights<M, R>(w0[R], w1[R]), ...);
+  (tile2_role_weights<kT2L, M, R>(w0[R], w1[R]), ...);
   T2ParamTable<M> t{};
   for (int s = 0; s < 2; ++s)
     for (int li = 0; li < kT2S * kT2S / 2; ++li) {
@@ -251,38 +220,10 @@ __device__ const T2ParamTable<M> kT2Params = t2_make_params<M>(std::make_integer
 // boundaries, summed per wave into g_t2_stamps (never touches an output).
 #ifdef DCTS_T2_STAMPS
 __device__ unsigned long long g_t2_stamps[16][16];
-#define T2_STAMP(slot)                                                            \
-  do {                                                                            \
-    unsigned long long t_;                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");  \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    acc_[slot] += t_ - last_;                                                     \
-    last_ = t_;                                                                   \
-  } while (0)
+#define T2_STAMP(slot) DCTS_STAMP_BODY(slot)
 #else
 #define T2_STAMP(slot) ((void)0)
 #endif
-
-__device__ __forceinline__ void t2_pin(float& x) { asm volatile("" : "+v"(x)); }
-
-// the L = 3 role network on 8 values held in registers: y[slot], constants by lane
-template <int M>
-__device__ __forceinline__ void t2_network(float (&y)[kT2S], const float (&rc)[T2Cfg<M>::NROT][4]) {
-  constexpr RolePlan<kT2L> plan{};
-  dcts::static_for<plan.NOPS>([&](auto i) DCTS_LAMBDA_INLINE {
-    constexpr int o = decltype(i)::value;
-    constexpr int a = plan.op_a[o], b = plan.op_b[o], r = plan.op_rot[o];
-    const float ya = y[a], yb = y[b];
-    if constexpr (r < 0) {
-      y[a] = ya + yb;
-      y[b] = ya - yb;
-    } else {
-      y[a] = ya * rc[r][0] + yb * rc[r][1];
-      y[b] = yb * rc[r][2] - ya * rc[r][3];
-    }
-  });
-}
 
 // Leaf transforms in stages, with scheduling barriers between the half-size sub-transforms and the
 // outputs handed to `sink(k, value)` as soon as a stage has them (an LDS store on axis A, a square on
@@ -601,42 +542,25 @@ __device__ __forceinline__ float t2_consume(int vid, lds_ptr zbuf, lds_cptr para
   return e;
 }
 
-// issue the loads of item (p, q) of a map for the column slots b in [B0, B1): buffer loads (one
-// wave-uniform descriptor per map, four lane offsets, the slot's offset as the scalar/immediate part)
-// instead of 64 per-lane 64-bit addresses; out-of-range reads return 0
+// issue loads of item (p, q) of a map: buffer loads (one wave-uniform descriptor per map, four lane
+// offsets, the slot's offset as the scalar/immediate part) instead of 64 per-lane 64-bit addresses;
+// out-of-range reads return 0
 // (lanes without an item - ok false - and the loads behind the last map of a workgroup - bytes 0 - read out of the
 // descriptor's range: the hardware returns 0 and makes no request. Round 2 let them re-read item 0 / the last map:
-// the PMC passes showed 1.18 x the algorithmic bytes for this kernel, profiles/r03_pmc_traffic_large_*.json)
-constexpr int kT2Out = 0x7ffffff0;
-template <int M, int B0, int B1>
-__device__ __forceinline__ void t2_load(const float* __restrict__ in_b, int p, int q, bool ok, float (&v)[kT2S][kT2S]) {
-  constexpr int N = T2Cfg<M>::N;
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in_b), 0, DCTS_T2_EXP == 3 ? 0 : N * N * 4, 0x00020000);
-  const int pe = p, po = M - 1 - p, qe = q, qo = M - 1 - q;
-  const int o_ee = ok ? (pe * N + qe) * 4 : kT2Out, o_eo = ok ? (pe * N + qo) * 4 : kT2Out, o_oe = ok ? (po * N + qe) * 4 : kT2Out,
-            o_oo = ok ? (po * N + qo) * 4 : kT2Out;
-  dcts::static_for<kT2S>([&](auto ia) DCTS_LAMBDA_INLINE {
-    constexpr int a = decltype(ia)::value;
-    dcts::static_for<B1 - B0>([&](auto ib) DCTS_LAMBDA_INLINE {
-      constexpr int b = B0 + decltype(ib)::value;
-      const int voff = (a % 2 == 0) ? ((b % 2 == 0) ? o_ee : o_eo) : ((b % 2 == 0) ? o_oe : o_oo);
-      v[a][b] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, (a * M * N + b * M) * 4, 0));
-    });
-  });
-}
-
-// the same for entries [I0, I1) of the load order (t2_load_slot)
-template <int M, int I0, int I1>
+// the PMC passes showed 1.18 x the algorithmic bytes for this kernel, profiles/r03_pmc_traffic_large_*.json).
+// Which loads: entries [I0, I1) of an order of the slots with b < VB. FIRST: the workgroup's first map, row slot by row
+// slot (a-major); else the order of t2_load_slot (set by set, as this map's outputs vacate the registers).
+template <int M, bool FIRST, int I0, int I1>
 __device__ __forceinline__ void t2_load_seq(const float* __restrict__ in_b, unsigned bytes, int p, int q, bool ok, float (&v)[kT2S][kT2S]) {
-  constexpr int N = T2Cfg<M>::N;
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in_b), 0, DCTS_T2_EXP == 3 ? 0u : bytes, 0x00020000);
+  constexpr int N = T2Cfg<M>::N, VB = T2Cfg<M>::VB;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in_b), 0, bytes, 0x00020000);
+  // the sample of slot (a, b) is mirrored along an axis whose slot index is odd: four lane offsets
   const int pe = p, po = M - 1 - p, qe = q, qo = M - 1 - q;
-  const int o_ee = ok ? (pe * N + qe) * 4 : kT2Out, o_eo = ok ? (pe * N + qo) * 4 : kT2Out, o_oe = ok ? (po * N + qe) * 4 : kT2Out,
-            o_oo = ok ? (po * N + qo) * 4 : kT2Out;
+  const int o_ee = ok ? (pe * N + qe) * 4 : kLaneOut, o_eo = ok ? (pe * N + qo) * 4 : kLaneOut, o_oe = ok ? (po * N + qe) * 4 : kLaneOut,
+            o_oo = ok ? (po * N + qo) * 4 : kLaneOut;
   dcts::static_for<(I1 > I0 ? I1 - I0 : 0)>([&](auto ii) DCTS_LAMBDA_INLINE {
-    constexpr int sl = t2_load_slot(I0 + decltype(ii)::value, T2Cfg<M>::VB);
+    constexpr int i = I0 + decltype(ii)::value;
+    constexpr int sl = FIRST ? (i / VB) * kT2S + i % VB : t2_load_slot(i, VB);
     static_assert(sl >= 0, "slot");
     constexpr int a = sl / kT2S, b = sl % kT2S;
     const int voff = (a % 2 == 0) ? ((b % 2 == 0) ? o_ee : o_eo) : ((b % 2 == 0) ? o_oe : o_oo);
@@ -675,7 +599,7 @@ __device__ __forceinline__ void t2_body(const Src& tb, lds_ptr zbuf, lds_ptr raw
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(last_)::"memory");
 #endif
   // tables -> LDS (read per map instead of living in registers)
-  for (int i = threadIdx.x; i < NROT * M * 4; i += blockDim.x) rot[i] = (&kT2Rot<M>.v[0][0][0])[i];
+  for (int i = threadIdx.x; i < NROT * M * 4; i += blockDim.x) rot[i] = (&kTile2Rot<kT2L, M>.v[0][0][0])[i];
   for (int i = threadIdx.x; i < 2 * (S * S / 2); i += blockDim.x) {
     const T2BlockParam& bp = (&kT2Params<M>.v[0][0])[i];
     params[i * 8 + 0] = __builtin_bit_cast(float, bp.tA);
@@ -712,7 +636,7 @@ __device__ __forceinline__ void t2_body(const Src& tb, lds_ptr zbuf, lds_ptr raw
     bool ok;
     item_pq(p, q, ok);
     const float* first = tile_in(tb, m);  // grid <= nmaps: every workgroup owns a map
-    t2_load<M, 0, Cfg::VB>(first, p, q, ok, v);
+    t2_load_seq<M, true, 0, Cfg::NV>(first, (unsigned)(Cfg::N * Cfg::N * 4), p, q, ok, v);
     if constexpr (Cfg::DB > 0) {
       for (int i = wave; i < Cfg::RAW_PIECES; i += kT2Waves) t2_dma_piece<M>(first, raw, i, lane_in);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces have landed (the barrier below publishes them)
@@ -760,7 +684,7 @@ __device__ __forceinline__ void t2_body(const Src& tb, lds_ptr zbuf, lds_ptr raw
             y[a] = raw[row * Cfg::RAWW + (b - Cfg::VB) * M + qq];
           });
         }
-        t2_network<M>(y, rp);
+        tile2_network<kT2L, NROT>(y, rp);
         dcts::static_for<S>([&](auto ia) DCTS_LAMBDA_INLINE { v[decltype(ia)::value][b] = y[decltype(ia)::value]; });
         // one network at a time: interleaved for ILP the eight of them run the registers out, and what
         // the allocator then spills are the long-lived samples / parked outputs
@@ -774,11 +698,11 @@ __device__ __forceinline__ void t2_body(const Src& tb, lds_ptr zbuf, lds_ptr raw
       // along b (the W axis) for every a: constants by q
       dcts::static_for<S>([&](auto ia) DCTS_LAMBDA_INLINE {
         constexpr int a = decltype(ia)::value;
-        t2_network<M>(v[a], rq);
+        tile2_network<kT2L, NROT>(v[a], rq);
         // the outputs exist HERE: LLVM otherwise sinks the networks down to the LDS stores of the set that
         // uses them (behind the barrier, interleaved with the stores' address arithmetic: 15 spilled VGPRs,
         // and every scratch reload waits vmcnt(0), i.e. for the next map's loads as well)
-        dcts::static_for<S>([&](auto ib) DCTS_LAMBDA_INLINE { t2_pin(v[a][decltype(ib)::value]); });
+        dcts::static_for<S>([&](auto ib) DCTS_LAMBDA_INLINE { tile2_pin(v[a][decltype(ib)::value]); });
         __builtin_amdgcn_sched_barrier(0);
       });
     }
@@ -837,14 +761,14 @@ __device__ __forceinline__ void t2_body(const Src& tb, lds_ptr zbuf, lds_ptr raw
           // the raw image is free since barrier #1 (phase A has read it): the next map's pieces, one
           // per wave and hook point (49 for 224x224; the 16 waves issue 16 at a time)
           constexpr int kk = decltype(k)::value;
-          if (DCTS_T2_EXP != 3 && more)
+          if (more)
             for (int i = wave + kT2Waves * kk; i < Cfg::RAW_PIECES; i += 3 * kT2Waves) t2_dma_piece<M>(nsrc, raw, i, launder(lane_in));
         }
         if constexpr (n > 0) {
           int p, q;
           bool ok;
           item_pq(p, q, ok);
-          t2_load_seq<M, i0, i0 + n>(nsrc, nbytes, p, q, ok, v);
+          t2_load_seq<M, false, i0, i0 + n>(nsrc, nbytes, p, q, ok, v);
         }
       };
     };
@@ -867,7 +791,7 @@ __device__ __forceinline__ void t2_body(const Src& tb, lds_ptr zbuf, lds_ptr raw
       int p, q;
       bool ok;
       item_pq(p, q, ok);
-      t2_load_seq<M, Cfg::hook_begin(6), Cfg::NV>(nsrc, nbytes, p, q, ok, v);
+      t2_load_seq<M, false, Cfg::hook_begin(6), Cfg::NV>(nsrc, nbytes, p, q, ok, v);
       __builtin_amdgcn_sched_barrier(0);
     }
     e = wave_sum_dpp(e);
@@ -898,19 +822,9 @@ __global__ __launch_bounds__(64 * kT2Waves) void k_tile2d(TileBatch tb, float* l
 
 #define DCTS_TILE2D_TABLE(X) X(224, 28)
 
-int t2_num_cus() {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
-      n = 256;
-    return n;
-  }();
-  return ncu;
-}
-
 template <int M>
 int launch_tile2d(const TileBatch& tb, hipStream_t st) {
-  const int ncu = t2_num_cus();
+  const int ncu = dctsi::num_cus();
   const long long grid = tb.total < ncu ? tb.total : ncu;  // LDS: one workgroup per CU
   hipLaunchKernelGGL((k_tile2d<M, false>), dim3((unsigned)grid), dim3(64 * kT2Waves), 0, st, tb, (float*)nullptr);
   return (int)hipGetLastError();
@@ -921,17 +835,7 @@ int launch_tile2d(const TileBatch& tb, hipStream_t st) {
 #ifdef DCTS_T2_DEV
 // development entry points (tools/t2_dev.py builds this file alone: seconds instead of minutes)
 extern "C" int t2_dev_run(const float* x, long long nmaps, int edge, float* out, void* stream) {
-  TileBatch tb;
-  for (int i = 0; i < kTileItems; ++i) {
-    tb.x[i] = x;
-    tb.out[i] = out;
-    tb.begin[i] = 0;
-  }
-  tb.begin[1] = tb.begin[kTileItems] = nmaps;
-  tb.map_elems = (long long)edge * edge;
-  tb.total = nmaps;
-  tb.count = 1;
-  return dctsi::dispatch_tile2d(edge, &tb, reinterpret_cast<hipStream_t>(stream));
+  return dctsi::dispatch_tile2d(edge, dctsi::single_tensor_batch(x, out, nmaps, (long long)edge * edge), reinterpret_cast<hipStream_t>(stream));
 }
 #ifdef DCTS_T2_STAMPS
 extern "C" int t2_dev_stamps(unsigned long long* host_out /*[16][16]*/, int reset) {
@@ -962,27 +866,12 @@ int dispatch_tile2d(int N, const TileBatch& tb, hipStream_t st) {
 int dispatch_tile2d_coeff(int N, const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps,
                           hipStream_t st) {
   if (N != 224) return DCTS_E_UNSUPPORTED;
-  if (!scratch || scratch_maps < 1) return DCTS_E_WORKSPACE;
   constexpr int M = 28;
-  for (long long m0 = 0; m0 < nmaps; m0 += scratch_maps) {
-    const long long nb = (nmaps - m0) < scratch_maps ? (nmaps - m0) : scratch_maps;
-    TileBatch tb;
-    for (int i = 0; i < kTileItems; ++i) {
-      tb.x[i] = x + m0 * (long long)N * N;
-      tb.out[i] = nullptr;  // the STORE instantiation writes no energies
-      tb.begin[i] = 0;
-    }
-    tb.begin[1] = tb.begin[kTileItems] = nb;
-    tb.map_elems = (long long)N * N;
-    tb.total = nb;
-    tb.count = 1;
-    const long long grid = nb < t2_num_cus() ? nb : t2_num_cus();  // as the energy launch: one persistent workgroup per CU
-    hipLaunchKernelGGL((k_tile2d<M, true>), dim3((unsigned)grid), dim3(64 * kT2Waves), 0, st, tb, scratch);
-    int rc = (int)hipGetLastError();
-    if (rc) return rc;
-    rc = launch_assemble<M, kT2L, false>(scratch, nb, out + m0 * (long long)N * N, st);
-    if (rc) return rc;
-  }
-  return DCTS_OK;
+  auto launch = [st](const TileBatch& tb, float* leaf) {
+    const long long grid = tb.total < num_cus() ? tb.total : num_cus();  // as the energy launch: one persistent workgroup per CU
+    hipLaunchKernelGGL((k_tile2d<M, true>), dim3((unsigned)grid), dim3(64 * kT2Waves), 0, st, tb, leaf);
+    return (int)hipGetLastError();
+  };
+  return run_coeff_chunks(launch, launch_assemble<M, kT2L, false>, N, x, nmaps, out, scratch, scratch_maps, st);
 }
 }  // namespace dctsi

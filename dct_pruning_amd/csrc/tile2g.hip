@@ -33,7 +33,7 @@
 
 #include "../../include/dctscore.h"
 #include "dcts_internal.h"  // has_tile2g[_pad], dispatch_tile2g[_pad], dispatch_tile2g_coeff
-#include "split_roles.hpp"
+#include "tile2_common.hpp"
 
 namespace {
 
@@ -119,15 +119,6 @@ struct G2Cfg {
   static_assert((long long)ZSET * 4 <= 156 * 1024, "LDS");
   static constexpr int NROT = RolePlan<L>{}.nrot;
   static constexpr int SLOTS = S * S, PER_SET = SLOTS / 2 / NSETS;  // samples per lane; slot pairs per lane and set
-  // 8-byte loads shared by neighbouring lanes (g2_load_pairs, DCTS_G2_PAIR=1): half the load instructions, but
-  // measured SLOWER on the same box for every shape (144 x 144: 45.3 -> 42.6 %, 128: 53.3 -> 50.0, 72: 49.6 -> 45.9 of
-  // the HBM peak at 8192 / 8192 / 32768 maps): the DPP exchange and the select instructions cost more than the load
-  // issue they save. Off.
-#ifndef DCTS_G2_PAIR
-  static constexpr bool PAIR = false;
-#else
-  static constexpr bool PAIR = (DCTS_G2_PAIR != 0);
-#endif
 };
 
 // Which set a block is in, its position in the set and the order of the passes: blocks sorted by the cost of
@@ -152,8 +143,9 @@ struct G2Sched {
         order[k - 1] = t;
       }
     // Two sets: by the parity of the block's row slot a. A lane loads the samples of the slots (a, b) and
-    // (a + 2, b) with ONE 8-byte instruction shared with its neighbour lane (g2_load_pairs): both must belong
-    // to the same set, so that their registers are vacated together.
+    // (a + 2, b) together (g2_load_pairs): both belong to the same set, so that their registers are vacated
+    // together. (The rule served the 8-byte paired loads that were measured slower and removed; it stays
+    // because it decides which block goes where.)
     int fill[NSETS] = {};
     for (int i = 0; i < NB; ++i) {
       const int s = (NSETS == 1) ? 0 : (plan.slot_of_role[order[i] / S] & 1), rank = fill[s]++;  // rank-th cheapest block of set s
@@ -169,26 +161,6 @@ struct G2Sched {
 template <int L, int NSETS>
 inline constexpr G2Sched<L, NSETS> kG2Sched{};
 
-// rotation constants (c, s, sigma*c, sigma*s), sigma = (-1)^j of the pair index: [rot][p][4]
-template <int L, int M>
-struct G2RotTable {
-  static constexpr int NROT = RolePlan<L>{}.nrot;
-  float v[NROT > 0 ? NROT : 1][M][4] = {};
-  constexpr G2RotTable() {
-    constexpr RotTable<M, L> t{};
-    for (int r = 0; r < NROT; ++r)
-      for (int p = 0; p < M; ++p) {
-        const float sg = RotTable<M, L>::sign0(r) * ((p & 1) ? -1.f : 1.f);
-        v[r][p][0] = t.c[r][p];
-        v[r][p][1] = t.s[r][p];
-        v[r][p][2] = sg * t.c[r][p];
-        v[r][p][3] = sg * t.s[r][p];
-      }
-  }
-};
-template <int L, int M>
-__device__ const G2RotTable<L, M> kG2Rot{};
-
 // per (set, li): leaf types and squared amplitude weights of the block (8 words)
 struct G2BlockParam {
   int tA, tB, block, pad;
@@ -198,20 +170,13 @@ template <int L, int M, int NSETS>
 struct G2ParamTable {
   G2BlockParam v[NSETS][(1 << (2 * L)) / NSETS] = {};
 };
-template <int L, int M, int R>
-constexpr void g2_role_weights(float& w0, float& w1) {
-  using Leaf = typename RoleLeaf<(M << L), L, R>::type;
-  const double a = Leaf::wt(true), b = Leaf::wt(false);
-  w0 = float(a * a);
-  w1 = float(b * b);
-}
 template <int L, int M, int NSETS, int... R>
 constexpr G2ParamTable<L, M, NSETS> g2_make_params(std::integer_sequence<int, R...>) {
   constexpr int S = 1 << L;
   constexpr RolePlan<L> plan{};
   constexpr G2Sched<L, NSETS> sch{};
   float w0[S] = {}, w1[S] = {};
-  (g2_role_weights<L, M, R>(w0[R], w1[R]), ...);
+  (tile2_role_weights<L, M, R>(w0[R], w1[R]), ...);
   G2ParamTable<L, M, NSETS> t{};
   for (int s = 0; s < NSETS; ++s)
     for (int li = 0; li < S * S / NSETS; ++li) {
@@ -232,58 +197,14 @@ __device__ const G2ParamTable<L, M, NSETS> kG2Params = g2_make_params<L, M, NSET
 template <int M, int PB, int LW>
 __device__ const G2LaneMap kG2Lanes{M, PB, LW};
 
-// Per-map sums: every lane leaves its sum in LDS and wave 0 adds the sixteen waves' values per lane (fixed order) and runs ONE
-// segmented reduction over the rows of a block after the next barrier - instead of a five-step shuffle reduction in each of the
-// sixteen waves at the end of every round. Same box, % of the HBM peak: 72 x 72 38.7 -> 41.9 (5760 maps), 49.6 -> 51-52 (32768);
-// 80: 41.7 -> 43.4; 144: 41.5 -> 42.4 (4992), 41 -> 43-44 (8192); 160: 39.8 -> 40.2. Bit-reproducible either way.
-#ifndef DCTS_G2_LATE_REDUCE
-#define DCTS_G2_LATE_REDUCE 1
-#endif
-// Waves without items skip the network and set-store phases, and the last of them takes the per-map sums: same box,
-// 160: 39.5 -> 40.4 %, 80: 42.9 -> 43.6 %, 112: 35.5 -> 36.0 % of the HBM peak (144 / 72 have items on every wave: unchanged path).
-#ifndef DCTS_G2_SKIP_IDLE
-#define DCTS_G2_SKIP_IDLE 1
-#endif
-#ifndef DCTS_G2_SKEW
-#define DCTS_G2_SKEW 0
-#endif
-#ifndef DCTS_G2_EXP
-#define DCTS_G2_EXP 0  // timing experiments (wrong results): 1 no codelet arithmetic, 2 no LDS traffic behind axis A's reads, 3 no loads of the next round
-#endif
+// Diagnostic build only (-DDCTS_G2_STAMPS, tools/g2_dev.py): s_memtime stamps at the phase boundaries, summed per wave into
+// g_g2_stamps (never touches an output).
 #ifdef DCTS_G2_STAMPS
 __device__ unsigned long long g_g2_stamps[16][16];
-#define G2_STAMP(slot)                                                            \
-  do {                                                                            \
-    unsigned long long t_;                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");  \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    acc_[slot] += t_ - last_;                                                     \
-    last_ = t_;                                                                   \
-  } while (0)
+#define G2_STAMP(slot) DCTS_STAMP_BODY(slot)
 #else
 #define G2_STAMP(slot) ((void)0)
 #endif
-
-__device__ __forceinline__ void g2_pin(float& x) { asm volatile("" : "+v"(x)); }
-
-// the L-level role network on 2^L values held in registers: y[slot], constants by lane
-template <int L, int NROT>
-__device__ __forceinline__ void g2_network(float (&y)[1 << L], const float (&rc)[NROT > 0 ? NROT : 1][4]) {
-  constexpr RolePlan<L> plan{};
-  dcts::static_for<plan.NOPS>([&](auto i) DCTS_LAMBDA_INLINE {
-    constexpr int o = decltype(i)::value;
-    constexpr int a = plan.op_a[o], b = plan.op_b[o], r = plan.op_rot[o];
-    const float ya = y[a], yb = y[b];
-    if constexpr (r < 0) {
-      y[a] = ya + yb;
-      y[b] = ya - yb;
-    } else {
-      y[a] = ya * rc[r][0] + yb * rc[r][1];
-      y[b] = yb * rc[r][2] - ya * rc[r][3];
-    }
-  });
-}
 
 // the group of G maps a round works on: all of one tensor (a TileBatch may hold several)
 struct G2Group {
@@ -338,16 +259,21 @@ template <int L, int NSETS>
 inline constexpr G2LoadOrder<L, NSETS> kG2LoadOrder{};
 
 typedef float g2_v2f __attribute__((ext_vector_type(2)));
-constexpr int g2_pi(int a) { return (a & 1) | ((a & 4) >> 1); }  // which register pair holds row slot a (.x: a & 2 == 0, .y: the slot two rows on)
+// which register pair holds row slot a (.x: a & 2 == 0, .y: the slot two rows on). The pairs are what the removed 8-byte
+// loads filled; they stay because the register assignment of every instantiation follows from them (a plain
+// float v[S][S] compiles to other code).
+constexpr int g2_pi(int a) { return (a & 1) | ((a & 4) >> 1); }
 
-// Loads of the item pair (g, p, 2k), (g, p, 2k + 1) - two neighbouring lanes - for the slot pairs [I0, I1) of the load
-// order. Single dwords per lane cost the vector-memory pipeline ~10 cycles per wave instruction here (every
-// instruction touches 4-7 cache lines: M-float row segments), and 64 of them per lane and round kept the waves
-// blocked on load issue for a quarter of the time. The columns of the two items are adjacent in memory, so the EVEN
-// lane fetches both items' samples of slot (a, b) with one 8-byte load and the ODD lane those of slot (a + 2, b) with
-// the same instruction (its lane offset points two row slots further): half the instructions. g2_exchange() hands
-// each lane its own two samples afterwards. Reads beyond the group's `bytes` return 0 (lanes without an item, maps
-// beyond a short group, "no next group").
+// Loads of this lane's item (g, p, q) for the slot pairs [I0, I1) of the load order: two single dwords per pair. They cost
+// the vector-memory pipeline ~10 cycles per wave instruction here (every instruction touches 4-7 cache lines: M-float
+// row segments), and 64 of them per lane and round keep the waves blocked on load issue for a quarter of the time.
+// (8-byte loads shared by neighbouring lanes - the even lane fetching both items' samples of slot (a, b), the odd lane
+// those of slot (a + 2, b), one DPP swap per pair afterwards - halved the instructions but were measured SLOWER on the same
+// box for every shape (144 x 144: 45.3 -> 42.6 %, 128: 53.3 -> 50.0, 72: 49.6 -> 45.9 % of the HBM peak at 8192 / 8192 /
+// 32768 maps): the exchange and the select instructions cost more than the load issue they saved. Removed; in history. The
+// pair-wise load order, the register pairs vp[][] and G2Sched's set rule remain from it: they fix the order of the loads
+// and which block goes where.)
+// Reads beyond the group's `bytes` return 0 (lanes without an item, maps beyond a short group, "no next group").
 // PAD (the cv2 path of torch2dct, utils/common.py:235-236, for an odd H: one zero row AND one zero column in front): the map
 // in memory is (N-1) x (N-1) with row pitch N-1; sample (r, c) of the padded tile is x[r-1][c-1], and row 0 / column 0 are
 // zeros. The descriptor's base is moved N floats in front of the group's first map, so that offset (r * (N-1) + c) * 4
@@ -359,10 +285,9 @@ struct G2Voffs {
   int ee_b0, oe_b0;        // PAD: column slot 0  (zero column for q == 0)
   int ee_ab;               // PAD: slot (0, 0)
 };
-template <int L, int M, int G, int NSETS, bool PAIR, int PAD, int I0, int I1>
+template <int L, int M, int G, int NSETS, int PAD, int I0, int I1>
 __device__ __forceinline__ void g2_load_pairs(const float* base, unsigned bytes, const G2Voffs& vo, g2_v2f (&vp)[(1 << L) / 2][1 << L]) {
   constexpr int S = 1 << L, N = M * S, NP = N - PAD;  // NP: row pitch in memory
-  static_assert(!(PAIR && PAD), "the paired loads assume aligned column pairs");
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base) - PAD * (NP + 1), 0,
                                                                       bytes ? bytes + PAD * (NP + 1) * 4 : 0u, 0x00020000);
   auto pick = [&](auto ia, auto ib) DCTS_LAMBDA_INLINE -> int {
@@ -375,33 +300,11 @@ __device__ __forceinline__ void g2_load_pairs(const float* base, unsigned bytes,
   dcts::static_for<(I1 > I0 ? I1 - I0 : 0)>([&](auto ii) DCTS_LAMBDA_INLINE {
     constexpr int sl = kG2LoadOrder<L, NSETS>.pair[I0 + decltype(ii)::value];
     constexpr int a = sl / S, b = sl % S;
-    if constexpr (PAIR) {
-      vp[g2_pi(a)][b] = __builtin_bit_cast(g2_v2f, __builtin_amdgcn_raw_buffer_load_b64(rs, pick(std::integral_constant<int, a>{}, std::integral_constant<int, b>{}),
-                                                                                         (a * M * NP + b * M) * 4, 0));
-    } else {  // every lane loads its own two samples of the slot pair, one dword each (the offsets point at its own column)
-      vp[g2_pi(a)][b].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-          rs, pick(std::integral_constant<int, a>{}, std::integral_constant<int, b>{}), (a * M * NP + b * M) * 4, 0));
-      vp[g2_pi(a)][b].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-          rs, pick(std::integral_constant<int, a + 2>{}, std::integral_constant<int, b>{}), ((a + 2) * M * NP + b * M) * 4, 0));
-    }
+    vp[g2_pi(a)][b].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+        rs, pick(std::integral_constant<int, a>{}, std::integral_constant<int, b>{}), (a * M * NP + b * M) * 4, 0));
+    vp[g2_pi(a)][b].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+        rs, pick(std::integral_constant<int, a + 2>{}, std::integral_constant<int, b>{}), ((a + 2) * M * NP + b * M) * 4, 0));
   });
-}
-
-// after the loads have landed: the even lane holds {its own, its neighbour's} sample of slot (a, b), the odd lane
-// {its neighbour's, its own} of slot (a + 2, b) (mirrored column slots b: the other way round); one DPP swap per
-// pair leaves both lanes with .x = their sample of (a, b) and .y = that of (a + 2, b)
-template <int B>
-__device__ __forceinline__ void g2_exchange(g2_v2f& r, bool odd) {
-  const float X = r.x, Y = r.y;
-  const float give = (B % 2 == 0) ? (odd ? X : Y) : (odd ? Y : X);
-  const float got = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, give), 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, true));
-  if constexpr (B % 2 == 0) {
-    r.x = odd ? got : X;
-    r.y = odd ? Y : got;
-  } else {
-    r.x = odd ? got : Y;
-    r.y = odd ? X : got;
-  }
 }
 
 // one leaf pass: PB blocks (the same (ra, rb) of the PB maps), both axes; returns the lane's weighted energy
@@ -420,19 +323,11 @@ __device__ __forceinline__ float g2_pass(lds_ptr zset, lds_cptr pp, int li, int 
     lds_ptr col = zset + (li * G + gl) * BS + j;
     float in[M], o[M];
     dcts::static_for<M>([&](auto i) DCTS_LAMBDA_INLINE { in[decltype(i)::value] = col[decltype(i)::value * RS]; });
-#if DCTS_G2_EXP == 1
-    dcts::static_for<M>([&](auto i) DCTS_LAMBDA_INLINE { o[decltype(i)::value] = in[decltype(i)::value] * 1.5f; });
-#else
     if constexpr (TA)
       dcts::Dct4<M>::run(in, o);
     else
       dcts::Dct2<M>::run(in, o);
-#endif
-#if DCTS_G2_EXP == 2
-    dcts::static_for<M>([&](auto i) DCTS_LAMBDA_INLINE { g2_pin(o[decltype(i)::value]); });
-#else
     if (act) dcts::static_for<M>([&](auto i) DCTS_LAMBDA_INLINE { col[decltype(i)::value * RS] = o[decltype(i)::value]; });
-#endif
   }
   // the wave's own LDS traffic is in order; only the compiler must not reorder
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -443,19 +338,11 @@ __device__ __forceinline__ float g2_pass(lds_ptr zset, lds_cptr pp, int li, int 
   const bool act = (map_b >> 16) != 0;
   lds_cptr row = zset + (li * G + gl) * BS + j * RS;
   float z[M], w[M];
-#if DCTS_G2_EXP == 2
-  dcts::static_for<M>([&](auto i) DCTS_LAMBDA_INLINE { z[decltype(i)::value] = __builtin_bit_cast(float, launder(map_b + decltype(i)::value)); });
-#else
   dcts::static_for<M>([&](auto i) DCTS_LAMBDA_INLINE { z[decltype(i)::value] = row[decltype(i)::value]; });
-#endif
-#if DCTS_G2_EXP == 1
-  dcts::static_for<M>([&](auto i) DCTS_LAMBDA_INLINE { w[decltype(i)::value] = z[decltype(i)::value] * 1.5f; });
-#else
   if constexpr (TB)
     dcts::Dct4<M>::run(z, w);
   else
     dcts::Dct2<M>::run(z, w);
-#endif
   if constexpr (STORE) {
     // debug / parity path: leaf outputs, unweighted, as [ra * M + k1][rb * M + k2] (k_assemble's layout)
     const int blk_id = __builtin_bit_cast(int, pp[2]);
@@ -495,7 +382,7 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
 #endif
   // tables -> LDS
   if constexpr (NROT > 0)
-    for (int i = threadIdx.x; i < NROT * M * 4; i += blockDim.x) rot[i] = (&kG2Rot<L, M>.v[0][0][0])[i];
+    for (int i = threadIdx.x; i < NROT * M * 4; i += blockDim.x) rot[i] = (&kTile2Rot<L, M>.v[0][0][0])[i];
   for (int i = threadIdx.x; i < NSETS * NBS; i += blockDim.x) {
     const G2BlockParam& bp = (&kG2Params<L, M, NSETS>.v[0][0])[i];
     params[i * 8 + 0] = __builtin_bit_cast(float, bp.tA);
@@ -521,11 +408,8 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
   const int ig = ok ? idx / (M * M) : 0;
   const int ir = ok ? idx - ig * (M * M) : 0;
   const int ip = ir / M, iq = ir - ip * M;
-  // lane offsets of the four mirrored quadrant kinds (with DCTS_G2_PAIR, 8-byte pairs: the even column of the lane pair, odd
-  // lanes two row slots further, see g2_load_pairs); lanes without an item read out of range (zeros, no traffic)
-  static_assert(M % 2 == 0, "lane pairs share a row");
+  // lane offsets of the four mirrored quadrant kinds; lanes without an item read out of range (zeros, no traffic)
   static_assert(!(STORE && PAD), "the coefficient path takes unpadded tiles");
-  constexpr int kOut = 0x7ffffff0;
   constexpr int NPITCH = N - PAD, MAPB = NPITCH * NPITCH * 4;  // row pitch (floats) and bytes of a map in memory
   // (`cnt`: maps in the group the offsets are for. Lanes of maps beyond a short group are out of range by their own
   // offset - with PAD the descriptor is N floats longer than the group's maps, so the range check alone would let the
@@ -533,26 +417,17 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
   auto voffs = [&](G2Voffs& vo, int cnt) DCTS_LAMBDA_INLINE {
     const int p = launder(ip), q = launder(iq), g = launder(ig);
     const bool ok = launder(idx) < Cfg::ITEMS && g < cnt;
-    if constexpr (Cfg::PAIR) {
-      const int q2 = q & ~1;
-      const int gbo = g * MAPB + ((q & 1) ? 2 * M * NPITCH * 4 : 0);
-      vo.ee = ok ? gbo + (p * NPITCH + q2) * 4 : kOut;
-      vo.eo = ok ? gbo + (p * NPITCH + (M - 2 - q2)) * 4 : kOut;
-      vo.oe = ok ? gbo + ((M - 1 - p) * NPITCH + q2) * 4 : kOut;
-      vo.oo = ok ? gbo + ((M - 1 - p) * NPITCH + (M - 2 - q2)) * 4 : kOut;
-    } else {
-      const int gbo = g * MAPB;
-      vo.ee = ok ? gbo + (p * NPITCH + q) * 4 : kOut;
-      vo.eo = ok ? gbo + (p * NPITCH + (M - 1 - q)) * 4 : kOut;
-      vo.oe = ok ? gbo + ((M - 1 - p) * NPITCH + q) * 4 : kOut;
-      vo.oo = ok ? gbo + ((M - 1 - p) * NPITCH + (M - 1 - q)) * 4 : kOut;
-    }
+    const int gbo = g * MAPB;
+    vo.ee = ok ? gbo + (p * NPITCH + q) * 4 : kLaneOut;
+    vo.eo = ok ? gbo + (p * NPITCH + (M - 1 - q)) * 4 : kLaneOut;
+    vo.oe = ok ? gbo + ((M - 1 - p) * NPITCH + q) * 4 : kLaneOut;
+    vo.oo = ok ? gbo + ((M - 1 - p) * NPITCH + (M - 1 - q)) * 4 : kLaneOut;
     if constexpr (PAD != 0) {
-      vo.ee_a0 = p == 0 ? kOut : vo.ee;
-      vo.eo_a0 = p == 0 ? kOut : vo.eo;
-      vo.ee_b0 = q == 0 ? kOut : vo.ee;
-      vo.oe_b0 = q == 0 ? kOut : vo.oe;
-      vo.ee_ab = (p == 0 || q == 0) ? kOut : vo.ee;
+      vo.ee_a0 = p == 0 ? kLaneOut : vo.ee;
+      vo.eo_a0 = p == 0 ? kLaneOut : vo.eo;
+      vo.ee_b0 = q == 0 ? kLaneOut : vo.ee;
+      vo.oe_b0 = q == 0 ? kLaneOut : vo.oe;
+      vo.ee_ab = (p == 0 || q == 0) ? kLaneOut : vo.ee;
     }
   };
   const int ngroups = gb.gbegin[gb.tb.count];
@@ -578,7 +453,7 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
   {
     G2Voffs vo;
     voffs(vo, cur.count);
-    g2_load_pairs<L, M, G, NSETS, Cfg::PAIR, PAD, 0, S * S / 2>(cur.base, (unsigned)(cur.count * MAPB), vo, vp);
+    g2_load_pairs<L, M, G, NSETS, PAD, 0, S * S / 2>(cur.base, (unsigned)(cur.count * MAPB), vo, vp);
   }
   __builtin_amdgcn_sched_barrier(0);
   long long pending = -1;  // a round whose partials wait for the workgroup sum
@@ -586,11 +461,14 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
   int pending_count = 0, pslot = 0, pending_slot = 0;
   auto finish = [&]() DCTS_LAMBDA_INLINE {
     if (pending >= 0) {
-#if DCTS_G2_LATE_REDUCE
-      // ONE wave - the last, which holds the fewest items or none: per lane the sixteen waves' sums in fixed order, then ONE
-      // segmented reduction over the rows of a block
-      // (wave 0 where every wave has items: 144 / 72 lose 2-3 % with the duty on a wave that also has a full share of items)
-      if (wave == ((DCTS_G2_SKIP_IDLE && Cfg::ITEMS <= (NW - 1) * 64) ? NW - 1 : 0)) {
+      // Per-map sums: every lane leaves its sum in LDS and ONE wave adds the sixteen waves' values per lane (fixed order) and runs
+      // ONE segmented reduction over the rows of a block after the next barrier. (A five-step shuffle reduction in each of the
+      // sixteen waves at the end of every round was measured slower on the same box, % of the HBM peak: 72 x 72 38.7 -> 41.9
+      // (5760 maps), 49.6 -> 51-52 (32768); 80: 41.7 -> 43.4; 144: 41.5 -> 42.4 (4992), 41 -> 43-44 (8192); 160: 39.8 -> 40.2;
+      // bit-reproducible either way. Removed; in history.)
+      // The wave: the last, where it holds no items (wave 0 where every wave has items: 144 / 72 lose 2-3 % with the duty on a
+      // wave that also has a full share of items)
+      if (wave == (Cfg::ITEMS <= (NW - 1) * 64 ? NW - 1 : 0)) {
         const int mb = launder(map_b);
         const int j = (mb >> 8) & 0xff;
         const bool act = (mb >> 16) != 0;
@@ -608,15 +486,6 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
         if constexpr (!STORE)
           if (act && j == 0 && (mb & 0xff) < pending_count) pending_out[mb & 0xff] = t * sc;
       }
-#else
-      if (wave == 0 && lane_in < pending_count) {
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < NW; ++i) t += partials[(pending_slot * NW + i) * G + lane_in];
-        constexpr float sc = float(4.0 / (double(N) * double(N)));
-        if constexpr (!STORE) pending_out[lane_in] = t * sc;
-      }
-#endif
       pending = -1;
     }
   };
@@ -625,21 +494,25 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
   for (; grp < ngroups; grp += gridDim.x) {
     // ---- A: role networks of this lane's item, both axes, in registers -----------------------------------
     // (G * M * M items on 1024 lanes: the last waves may hold none at all - 800 items at 160 and 80, 784 at 112 - and skip
-    // the networks and the stores of the sets: wave-uniform, and three waves fewer compete for the VALUs and the LDS there)
-    if (DCTS_G2_SKIP_IDLE == 0 || wave * 64 < Cfg::ITEMS) {
+    // the networks and the stores of the sets: wave-uniform, and three waves fewer compete for the VALUs and the LDS there.
+    // Against every wave running them, same box: 160: 39.5 -> 40.4 %, 80: 42.9 -> 43.6 %, 112: 35.5 -> 36.0 % of the HBM peak;
+    // 144 / 72 have items on every wave.)
+    if (wave * 64 < Cfg::ITEMS) {
       const int p = launder(ip), q = launder(iq);
       float rp[NROT > 0 ? NROT : 1][4];
       dcts::static_for<NROT>([&](auto ir_) DCTS_LAMBDA_INLINE {
         constexpr int r = decltype(ir_)::value;
         dcts::static_for<4>([&](auto ic) DCTS_LAMBDA_INLINE { rp[r][decltype(ic)::value] = rot[(r * M + p) * 4 + decltype(ic)::value]; });
       });
-      const bool odd = (launder(lane_in) & 1) != 0;
+      // (An opaque copy of the lane index, one v_mov per round: what is left of the removed paired loads' exchange, which
+      // asked here whether the lane is odd. Nothing reads it; dropping it changes the instruction stream and is left to a
+      // change that measures the kernels.)
+      (void)launder(lane_in);
       dcts::static_for<S>([&](auto ib) DCTS_LAMBDA_INLINE {  // along a (the H axis) for every b: constants by p
         constexpr int b = decltype(ib)::value;
-        if constexpr (Cfg::PAIR) dcts::static_for<S / 2>([&](auto ipair) DCTS_LAMBDA_INLINE { g2_exchange<b>(vp[decltype(ipair)::value][b], odd); });
         float y[S];
         dcts::static_for<S>([&](auto ia) DCTS_LAMBDA_INLINE { y[decltype(ia)::value] = vget(ia, ib); });
-        g2_network<L, NROT>(y, rp);
+        tile2_network<L, NROT>(y, rp);
         dcts::static_for<S>([&](auto ia) DCTS_LAMBDA_INLINE { vset(ia, ib, y[decltype(ia)::value]); });
         __builtin_amdgcn_sched_barrier(0);
       });
@@ -651,10 +524,10 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
       dcts::static_for<S>([&](auto ia) DCTS_LAMBDA_INLINE {  // along b (the W axis) for every a: constants by q
         float y[S];
         dcts::static_for<S>([&](auto ib) DCTS_LAMBDA_INLINE { y[decltype(ib)::value] = vget(ia, ib); });
-        g2_network<L, NROT>(y, rq);
+        tile2_network<L, NROT>(y, rq);
         // the outputs exist HERE (LLVM otherwise sinks the networks behind the barrier, down to the LDS stores)
         dcts::static_for<S>([&](auto ib) DCTS_LAMBDA_INLINE {
-          g2_pin(y[decltype(ib)::value]);
+          tile2_pin(y[decltype(ib)::value]);
           vset(ia, ib, y[decltype(ib)::value]);
         });
         __builtin_amdgcn_sched_barrier(0);
@@ -666,17 +539,13 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
     finish();
     const bool more = grp + (int)gridDim.x < ngroups;
     const G2Group nxt = g2_group<G>(gb, more ? grp + (int)gridDim.x : grp, launder(gbeg_lane));
-#if DCTS_G2_EXP == 3
-    const unsigned nbytes = 0u;
-#else
     const unsigned nbytes = more ? (unsigned)(nxt.count * MAPB) : 0u;  // no next group: every load reads "out of range"
-#endif
     const long long map0 = STORE ? ((long long)grp * G) : 0;  // coefficient path: one tensor, groups are consecutive maps
     float e_acc = 0.f;
     dcts::static_for<NSETS>([&](auto iset) DCTS_LAMBDA_INLINE {
       constexpr int SET = decltype(iset)::value;
       // ---- this set's leaf-block samples -> LDS ------------------------------------------------------------
-      if (DCTS_G2_SKIP_IDLE == 0 || wave * 64 < Cfg::ITEMS) {
+      if (wave * 64 < Cfg::ITEMS) {
         const int p = launder(ip), q = launder(iq), g = launder(ig);
         const int dump = NBS * G * BS + (launder(lane_in) & 3);  // lanes without an item store behind the set
         const int gofs = g * BS;
@@ -699,12 +568,8 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
       G2_STAMP(2 + 4 * SET);
       lds_barrier();
       G2_STAMP(3 + 4 * SET);
-#if DCTS_G2_SKEW > 0
-      // Released together, the sixteen waves run their passes in lock step: all read LDS, then all compute, then
-      // all write - the LDS pipe and the VALUs take turns. Half of the waves (two of the four on every SIMD)
-      // start about one LDS phase late, so that one half's LDS traffic runs beside the other half's arithmetic.
-      if (wave >= NW / 2) __builtin_amdgcn_s_sleep(DCTS_G2_SKEW);
-#endif
+      // (Released together, the sixteen waves run their passes in lock step: all read LDS, then all compute, then all write.
+      // Starting half of the waves one LDS phase late - s_sleep of 6-20 x 64 cycles here - had no effect. Removed; in history.)
       // ---- leaf passes of this wave, the next round's samples trickled into the vacated registers ---------
       G2Voffs vo;
       voffs(vo, nxt.count);
@@ -717,14 +582,14 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
         constexpr int i0 = SET * Cfg::PER_SET + (Cfg::PER_SET * PASS) / PPW, i1 = SET * Cfg::PER_SET + (Cfg::PER_SET * (PASS + 1)) / PPW;
         constexpr int ih = i0 + (i1 - i0) / 2;
         G2_STAMP(4 + 4 * SET);
-        g2_load_pairs<L, M, G, NSETS, Cfg::PAIR, PAD, i0, ih>(nxt.base, nbytes, vo, vp);
+        g2_load_pairs<L, M, G, NSETS, PAD, i0, ih>(nxt.base, nbytes, vo, vp);
         __builtin_amdgcn_sched_barrier(0);
         G2_STAMP(13);
         float e = g2_pass_dispatch<L, M, G, STORE>(vid, zbuf, pp, li, launder(map_a), launder(map_b), leaf_out, map0, cur.count);
         asm volatile("" : "+v"(e));
         __builtin_amdgcn_sched_barrier(0);
         G2_STAMP(4 + 4 * SET);
-        g2_load_pairs<L, M, G, NSETS, Cfg::PAIR, PAD, ih, i1>(nxt.base, nbytes, vo, vp);
+        g2_load_pairs<L, M, G, NSETS, PAD, ih, i1>(nxt.base, nbytes, vo, vp);
         __builtin_amdgcn_sched_barrier(0);
         G2_STAMP(13);
         e_acc += e;
@@ -736,24 +601,7 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
       }
     });
     // ---- per-map sums: over the rows of a block (lanes of a group), then over the waves ---------------------
-#if DCTS_G2_LATE_REDUCE
-    partials[(pslot * NW + wave) * 64 + launder(lane_in)] = e_acc;  // lanes outside a block hold 0; summed by wave 0 (finish)
-#else
-    {
-      const int mb = launder(map_b);
-      const int j = (mb >> 8) & 0xff;
-      const bool act = (mb >> 16) != 0;
-      float e = e_acc;
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) {
-        if (off < M) {
-          const float t = __shfl_down(e, off, 64);
-          if (act && j + off < M) e += t;
-        }
-      }
-      if (act && j == 0) partials[(pslot * NW + wave) * G + (mb & 0xff)] = e;
-    }
-#endif
+    partials[(pslot * NW + wave) * 64 + launder(lane_in)] = e_acc;  // lanes outside a block hold 0; summed by one wave (finish)
     pending = grp;
     pending_out = cur.out;
     pending_count = cur.count;
@@ -774,11 +622,7 @@ __device__ __forceinline__ void g2_body(const G2Batch& gb, lds_ptr zbuf, lds_ptr
 // apart and fill each other's barrier waits and LDS / VALU / load-issue phases
 template <int L, int M, int G>
 constexpr int g2_wgs_per_cu() {
-#ifdef DCTS_G2_ONE_WG
-  return 1;
-#else
   return (L == 2 && (long long)(G2Cfg<L, M, G>::ZSET + 2048) * 4 * 2 <= 160 * 1024) ? 2 : 1;
-#endif
 }
 
 template <int L, int M, int G, bool STORE, int PAD = 0>
@@ -787,7 +631,7 @@ __global__ __launch_bounds__((64 * kG2Waves), (4 * g2_wgs_per_cu<L, M, G>())) vo
   __shared__ __attribute__((aligned(16))) float zbuf[Cfg::ZSET];
   __shared__ __attribute__((aligned(16))) float rot[(Cfg::NROT > 0 ? Cfg::NROT : 1) * M * 4];
   __shared__ __attribute__((aligned(16))) float params[Cfg::NSETS * Cfg::NBS * 8];
-  __shared__ float partials[2 * kG2Waves * (DCTS_G2_LATE_REDUCE ? 64 : G)];
+  __shared__ float partials[2 * kG2Waves * 64];
   g2_body<L, M, G, STORE, PAD>(gb, (lds_ptr)zbuf, (lds_ptr)rot, (lds_ptr)params, (lds_ptr)partials, leaf_out);
 }
 
@@ -799,16 +643,6 @@ __global__ __launch_bounds__((64 * kG2Waves), (4 * g2_wgs_per_cu<L, M, G>())) vo
 #ifndef DCTS_TILE2G_PAD_TABLE
 #define DCTS_TILE2G_PAD_TABLE(X) X(72, 2, 18, 3) X(80, 2, 20, 2) X(144, 3, 18, 3) X(160, 3, 20, 2)
 #endif
-
-int g2_num_cus() {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
-      n = 256;
-    return n;
-  }();
-  return ncu;
-}
 
 // groups of G maps, never across tensors; DCTS_E_SHAPE if they do not fit an int (2^31 groups: not a real launch)
 template <int G>
@@ -832,7 +666,7 @@ int launch_tile2g(const TileBatch& tb, hipStream_t st) {
   if (rc) return rc;
   const long long groups = gb.gbegin[tb.count];
   if (groups < 1) return DCTS_OK;
-  const long long cap = (long long)g2_num_cus() * g2_wgs_per_cu<L, M, G>();  // one residency, persistent over rounds
+  const long long cap = (long long)dctsi::num_cus() * g2_wgs_per_cu<L, M, G>();  // one residency, persistent over rounds
   const long long grid = groups < cap ? groups : cap;
   hipLaunchKernelGGL((k_tile2g<L, M, G, false, PAD>), dim3((unsigned)grid), dim3(64 * kG2Waves), 0, st, gb, (float*)nullptr);
   return (int)hipGetLastError();
@@ -841,36 +675,21 @@ int launch_tile2g(const TileBatch& tb, hipStream_t st) {
 template <int L, int M, int G>
 int coeff_tile2g(const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps, hipStream_t st) {
   constexpr int N = M << L;
-  if (!scratch || scratch_maps < 1) return DCTS_E_WORKSPACE;
-  for (long long m0 = 0; m0 < nmaps; m0 += scratch_maps) {
-    const long long nb = (nmaps - m0) < scratch_maps ? (nmaps - m0) : scratch_maps;
-    TileBatch tb;
-    for (int i = 0; i < kTileItems; ++i) {
-      tb.x[i] = x + m0 * (long long)N * N;
-      tb.out[i] = nullptr;  // the STORE instantiation writes no energies
-      tb.begin[i] = 0;
-    }
-    tb.begin[1] = tb.begin[kTileItems] = nb;
-    tb.map_elems = (long long)N * N;
-    tb.total = nb;
-    tb.count = 1;
-    G2Batch gb;
-    const int rcb = g2_make_batch<G>(tb, gb);
-    if (rcb) return rcb;
-    const long long groups = gb.gbegin[1];
-    const long long grid = groups < g2_num_cus() ? groups : g2_num_cus();
+  auto launch = [st](const TileBatch& tb, float* leaf) {
 #ifndef DCTS_G2_NOSTORE
-    hipLaunchKernelGGL((k_tile2g<L, M, G, true>), dim3((unsigned)grid), dim3(64 * kG2Waves), 0, st, gb, scratch);
+    G2Batch gb;
+    const int rc = g2_make_batch<G>(tb, gb);
+    if (rc) return rc;
+    const long long groups = gb.gbegin[1];
+    const long long grid = groups < dctsi::num_cus() ? groups : dctsi::num_cus();
+    hipLaunchKernelGGL((k_tile2g<L, M, G, true>), dim3((unsigned)grid), dim3(64 * kG2Waves), 0, st, gb, leaf);
+    return (int)hipGetLastError();
 #else
-    (void)grid;
-    return DCTS_E_UNSUPPORTED;  // development build without the coefficient instantiations
+    (void)st;
+    return (int)DCTS_E_UNSUPPORTED;  // development build without the coefficient instantiations
 #endif
-    int rc = (int)hipGetLastError();
-    if (rc) return rc;
-    rc = launch_assemble<M, L, false>(scratch, nb, out + m0 * (long long)N * N, st);
-    if (rc) return rc;
-  }
-  return DCTS_OK;
+  };
+  return run_coeff_chunks(launch, launch_assemble<M, L, false>, N, x, nmaps, out, scratch, scratch_maps, st);
 }
 
 }  // namespace
@@ -878,30 +697,11 @@ int coeff_tile2g(const float* x, long long nmaps, float* out, float* scratch, lo
 #ifdef DCTS_G2_DEV
 // development entry points (tools/g2_dev.py builds this file alone: seconds instead of minutes)
 extern "C" int g2_dev_run(const float* x, long long nmaps, int edge, float* out, void* stream) {
-  TileBatch tb;
-  for (int i = 0; i < kTileItems; ++i) {
-    tb.x[i] = x;
-    tb.out[i] = out;
-    tb.begin[i] = 0;
-  }
-  tb.begin[1] = tb.begin[kTileItems] = nmaps;
-  tb.map_elems = (long long)edge * edge;
-  tb.total = nmaps;
-  tb.count = 1;
-  return dctsi::dispatch_tile2g(edge, &tb, reinterpret_cast<hipStream_t>(stream));
+  return dctsi::dispatch_tile2g(edge, dctsi::single_tensor_batch(x, out, nmaps, (long long)edge * edge), reinterpret_cast<hipStream_t>(stream));
 }
 extern "C" int g2_dev_run_pad(const float* x, long long nmaps, int edge_padded, float* out, void* stream) {
-  TileBatch tb;
-  for (int i = 0; i < kTileItems; ++i) {
-    tb.x[i] = x;
-    tb.out[i] = out;
-    tb.begin[i] = 0;
-  }
-  tb.begin[1] = tb.begin[kTileItems] = nmaps;
-  tb.map_elems = (long long)(edge_padded - 1) * (edge_padded - 1);
-  tb.total = nmaps;
-  tb.count = 1;
-  return dctsi::dispatch_tile2g_pad(edge_padded, &tb, reinterpret_cast<hipStream_t>(stream));
+  return dctsi::dispatch_tile2g_pad(edge_padded, dctsi::single_tensor_batch(x, out, nmaps, (long long)(edge_padded - 1) * (edge_padded - 1)),
+                                    reinterpret_cast<hipStream_t>(stream));
 }
 extern "C" int g2_dev_coeff(const float* x, long long nmaps, int edge, float* out, float* scratch, long long scratch_maps, void* stream) {
   return dctsi::dispatch_tile2g_coeff(edge, x, nmaps, out, scratch, scratch_maps, reinterpret_cast<hipStream_t>(stream));

@@ -6,6 +6,8 @@ build (in the container; one shape compiles in about a minute):
   hipcc -O3 -std=c++17 -fPIC -shared --offload-arch=gfx950 -Wno-inline-asm -Wno-pass-failed -fno-slp-vectorize \
         -DDCTS_G2_DEV [-DDCTS_G2_STAMPS] [-DDCTS_G2_NOSTORE] ['-DDCTS_TILE2G_TABLE(X)=X(144,3,18,3)'] \
         -o build_dev/libg2.so dct_pruning_amd/csrc/tile2g.hip
+(STAMPS: phase stamps; NOSTORE: no coefficient instantiations; the table override: one shape. None changes a result. The
+removal experiments, the paired 8-byte loads and the other A/B switches were removed from the kernel.)
 run (GPU box): tools/g2_dev.py build_dev/libg2.so [edge[:nmaps] ...] [--coeff]
 """
 import ctypes

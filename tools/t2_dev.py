@@ -4,7 +4,10 @@ timing, Parseval check, optional phase stamps.
 
 build (in the container, seconds):
   hipcc -O3 -std=c++17 -fPIC -shared --offload-arch=gfx950 -Wno-inline-asm -Wno-pass-failed -fno-slp-vectorize \
-        -DDCTS_T2_DEV [-DDCTS_T2_STAMPS] [-DDCTS_T2_BEARLY=k] -o build_dev/libt2[_stamps].so dct_pruning_amd/csrc/tile2d.hip
+        -DDCTS_T2_DEV [-DDCTS_T2_STAMPS] [-DDCTS_T2_DMACOLS=k] ['-DDCTS_T2_HOOKS=4,4,4,12,12,12'] \
+        -o build_dev/libt2[_stamps].so dct_pruning_amd/csrc/tile2d.hip
+(DMACOLS: column slots of the next map that land in LDS instead of registers; HOOKS: its loads per hook point. Both are
+tuning switches that keep the results. The replay and load-order experiment switches were removed from the kernel.)
 run (GPU box): tools/t2_dev.py build_dev/libt2.so [edge:nmaps ...]
 """
 import ctypes
