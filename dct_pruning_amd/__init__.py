@@ -9,7 +9,9 @@ rank (rank_nc, imp_score(criterion="rank")), shares everything above the kernel,
 DCT energy spectrum (band_energy_nc, imp_score(criterion="bands"), bands.py: K frequency bands per map in one pass),
 and a fourth, the spectral entropy of the DCT coefficients (spectral_entropy_nc, imp_score(criterion="entropy")): one
 number per map that does depend on the transform. A fifth looks at more than one map at a time: the summed distance of
-every map to the other maps of its layer (gm_distance_nc, imp_score(criterion="gm")), FPGM's geometric-median rule on feature maps.
+every map to the other maps of its layer (gm_distance_nc, imp_score(criterion="gm")), FPGM's geometric-median rule on feature maps;
+its terms, the [C, C] matrix of pair distances per layer (gm_pair_matrix, imp_score(criterion="gm", gm_pairs=True)), feed the
+host-side selection rules of pairs.py (row sum, nearest neighbour, farthest point).
 """
 from .ops import (  # noqa: F401
     ALGO_AUTO,
@@ -29,6 +31,7 @@ from .ops import (  # noqa: F401
     energy_multi,
     energy_nc,
     gm_distance_nc,
+    gm_pair_matrix,
     has_band_kernel,
     has_codelet,
     has_entropy_kernel,
@@ -39,4 +42,4 @@ from .ops import (  # noqa: F401
     weighted_energy_nc,
 )
 
-__all__ = ["energy_nc", "energy_multi", "energy_mixed", "dct2d", "batch_sum", "has_codelet", "weighted_energy_nc", "rank_nc", "band_energy_nc", "has_band_kernel", "has_half_kernel", "has_nhwc_kernel", "spectral_entropy_nc", "has_entropy_kernel", "gm_distance_nc", "ALGO_AUTO", "ALGO_DIRECT", "ALGO_CODELET", "ALGO_SPLIT", "ALGO_PREFETCH", "ALGO_FUSED", "ALGO_PIPE", "ALGO_LANE", "ALGO_TILE2D", "ALGO_RECT"]
+__all__ = ["energy_nc", "energy_multi", "energy_mixed", "dct2d", "batch_sum", "has_codelet", "weighted_energy_nc", "rank_nc", "band_energy_nc", "has_band_kernel", "has_half_kernel", "has_nhwc_kernel", "spectral_entropy_nc", "has_entropy_kernel", "gm_distance_nc", "gm_pair_matrix", "ALGO_AUTO", "ALGO_DIRECT", "ALGO_CODELET", "ALGO_SPLIT", "ALGO_PREFETCH", "ALGO_FUSED", "ALGO_PIPE", "ALGO_LANE", "ALGO_TILE2D", "ALGO_RECT"]

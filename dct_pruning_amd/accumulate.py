@@ -10,6 +10,12 @@ DeviceBatchAccumulator  many hook points at once (single-sweep harness): the per
                   a batch are deferred and issued as ONE launch
                   (dcts_running_mean_update_multi_f32) when the next batch starts or the
                   scores are read.
+PairAccumulator   the pair matrices of imp_score(criterion="gm", gm_pairs=True): a [c, r] matrix per batch that is already
+                  summed over the batch's samples. The fp32 sum of the batch matrices in batch order, divided once by the
+                  number of samples when the scores are read. A host form (every batch matrix comes to the CPU) and a device
+                  form (the sum stays where the matrices are); both are elementwise fp32 adds in the same order and the one
+                  division is done on the host, so both give the same bytes. Not the three-rounding running mean above:
+                  nothing in the reference defines a sequence to reproduce here.
 """
 import torch
 
@@ -132,3 +138,23 @@ class DeviceBatchAccumulator:
     def scores(self, key):
         self.flush()
         return self.state[key][0].cpu().numpy()
+
+
+class PairAccumulator:
+    def __init__(self, device=None):
+        """device None: the host form; a device: the sum is kept there."""
+        self.device = None if device is None else torch.device(device)
+        self.sum, self.total = None, 0
+
+    def update(self, matrix, samples):
+        """matrix: [c, r] fp32, the distances of one batch summed over its `samples` samples."""
+        m = matrix.detach().to("cpu" if self.device is None else self.device, torch.float32)
+        if self.sum is None:
+            self.sum = torch.zeros_like(m)
+        elif self.sum.shape != m.shape:
+            raise ValueError("expected a %s pair matrix, got %s" % (tuple(self.sum.shape), tuple(m.shape)))
+        self.sum = self.sum + m
+        self.total += int(samples)
+
+    def scores(self):
+        return (self.sum.cpu() / float(self.total)).numpy()

@@ -8,7 +8,7 @@
 // 2-D DCT-II and the squared coefficients are reduced to one fp32 energy per map.
 //
 // The kernel families are units of their own (codelet.hip, split.hip, fused.hip, fused2.hip, pipe.hip, tile2d.hip,
-// tile2g.hip, rect.hip, rank.hip, band.hip, entropy.hip, gm.hip, half.hip, nhwc.hip, direct.hip: the cosine-matrix fallback for any
+// tile2g.hip, rect.hip, rank.hip, band.hip, entropy.hip, gm.hip, gm_pairs.hip, half.hip, nhwc.hip, direct.hip: the cosine-matrix fallback for any
 // (H, W) <= DCTS_MAX_EDGE, reduce.hip: batch sum, running mean, weighted reduction). What stays here of the direct family is
 // the memo of its basis tables: which workspace holds which tables is host policy.
 #include <hip/hip_runtime.h>
@@ -663,6 +663,39 @@ int dcts_gm_distance_metric_f32(const float* x, int64_t N, int64_t C_total, int6
   char* ws = reinterpret_cast<char*>(workspace);
   return dispatch_gm_metric(g, metric == DCTS_GM_CORRELATION, reinterpret_cast<float2*>(ws), reinterpret_cast<float2*>(ws + scored),
                             out_nc, st);
+}
+
+// ---- the pair matrix (gm_pairs.hip) -------------------------------------------------------------------------------------
+// The workspace: [the (mu, s) pairs of the scored range][those of the reference range] as dcts_gm_distance_metric_f32 lays them
+// out (a metric only), then [S][c_count][r_count] partial matrices where the samples are cut into S > 1 slices.
+int32_t dcts_gm_pairs_slices(int64_t N, int32_t r_count) { return gm_pair_slices(N, r_count); }
+
+size_t dcts_gm_pairs_workspace_bytes(int32_t metric, int64_t N, int32_t c_count, int32_t r_count) {
+  if (metric != DCTS_GM_L2 && metric != DCTS_GM_COSINE && metric != DCTS_GM_CORRELATION) return 0;
+  if (N <= 0 || c_count <= 0 || r_count <= 0) return 0;
+  return dcts_gm_workspace_bytes(metric, N, c_count, r_count) + gm_pair_partial_bytes(gm_pair_slices(N, r_count), c_count, r_count);
+}
+
+int dcts_gm_pairs_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN, int64_t strideC,
+                      int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count, int32_t r_begin, int32_t r_count,
+                      float* out_cr, void* stream, int32_t metric, void* workspace, size_t workspace_bytes) {
+  GmGeom g;
+  if (const int rc = gm_geom(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, r_begin, r_count, out_cr, &g))
+    return rc;
+  if (metric != DCTS_GM_L2 && metric != DCTS_GM_COSINE && metric != DCTS_GM_CORRELATION) return DCTS_E_UNSUPPORTED;
+  const size_t stats = dcts_gm_workspace_bytes(metric, N, c_count, r_count);
+  const size_t need = stats + gm_pair_partial_bytes(gm_pair_slices(N, r_count), c_count, r_count);
+  char* ws = reinterpret_cast<char*>(workspace);
+  if (need) {  // one slice without a metric needs none: NULL / 0 are fine
+    if (!workspace) return DCTS_E_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return DCTS_E_ALIGN;
+    if (workspace_bytes < need) return DCTS_E_WORKSPACE;
+    basis_forget_range(workspace, need);  // the pairs and partials overwrite whatever basis tables lay there
+  }
+  const size_t scored = stats ? gm_stats_bytes(N, c_count) : 0;
+  return dispatch_gm_pairs(g, metric == DCTS_GM_L2 ? -1 : (metric == DCTS_GM_CORRELATION ? 1 : 0), reinterpret_cast<float2*>(ws),
+                           reinterpret_cast<float2*>(ws + scored), reinterpret_cast<float*>(ws + stats), out_cr,
+                           reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- fp16 / bf16 inputs (half.hip) -----------------------------------------------------------------------------------

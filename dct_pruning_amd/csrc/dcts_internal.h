@@ -213,6 +213,16 @@ int dispatch_gm(const GmGeom& g, float* out, hipStream_t st);
 // by a launch of their own in front of the distance kernel. center: mu is the map's mean (correlation), else 0 (cosine).
 inline size_t gm_stats_bytes(long long N, int count) { return align_up((size_t)N * (size_t)count * sizeof(float2), 256); }
 int dispatch_gm_metric(const GmGeom& g, bool center, float2* sa, float2* sb, float* out, hipStream_t st);
+int launch_gm_stats(const GmGeom& g, bool center, int begin, int count, float2* pairs, hipStream_t st);  // one range's pairs
+
+// ---- gm_pairs.hip: every distance between a scored and a reference map, summed over the samples (dcts_gm_pairs_f32) --------
+// out: [c_count][r_count]. The samples are cut into gm_pair_slices(N, r_count) slices (grid_caps.h); with more than one, the
+// slices' matrices go to `partials`, gm_pair_partial_bytes() long, and a second launch adds them. center: -1 for the plain
+// distance, else 0 (cosine) / 1 (correlation) with sa / sb as for dispatch_gm_metric.
+inline size_t gm_pair_partial_bytes(int slices, int c_count, int r_count) {
+  return slices > 1 ? align_up((size_t)slices * (size_t)c_count * (size_t)r_count * sizeof(float), 256) : 0;
+}
+int dispatch_gm_pairs(const GmGeom& g, int center, float2* sa, float2* sb, float* partials, float* out, hipStream_t st);
 
 // ---- half.hip: fp16 / bf16 inputs (dcts_energy_typed) -------------------------------------------------------------
 // MapGeom for 2-byte elements (raw bits; the dtype travels beside it). Rows are dense: strideH == W.

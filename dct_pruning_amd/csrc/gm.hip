@@ -33,77 +33,19 @@
 // 256 bytes a channel contributes to a chunk), else single dwords (a wave per channel row). Both leave the same LDS image, so
 // the same bits come out. Nothing is prefetched into registers: at 94 / 120 VGPRs and 34 KiB of LDS four workgroups share a
 // CU, and one stages while the others compute (DESIGN.md 7h has the measurement against a register-prefetching version).
+// stage_tile, unit, pair_step and the tile constants are in gm_common.hpp, which k_gm_pairs (gm_pairs.hip) shares.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/dctscore.h"
 #include "dcts_internal.h"
+#include "gm_common.hpp"
 #include "grid_caps.h"
 
 using namespace dctsi;
 
 namespace {
-
-constexpr int TS = kGmTS, TR = kGmTR, KP = kGmKP, LD = kGmLD, THREADS = kGmThreads;
-static_assert(TS == 64 && TR == 64 && THREADS == 256, "thread (ty, tx) of 16 x 16 owns rows ty + 16 i and columns tx + 16 j, i, j < 4");
-static_assert(KP % 4 == 0 && LD % 4 == 0 && (LD / 4) % 2 == 1 && LD >= KP, "16-byte rows, an odd number of 16-byte slots apart");
-
-// an element of a unit map from the element of the map and the map's (mu, s): see stage_tile
-__device__ __forceinline__ float unit(float x, float2 ms) { return __builtin_fmaf(x - ms.x, ms.y, 0.f); }
-
-// One tile's share of a chunk, global -> LDS: channels [ch0, ch0 + 64) of the range that starts at `base` (element 0 of its
-// channel 0 in this sample) and has `count` channels, elements [p0, p0 + KP). Out of range: zeros, and no load. Four loads are
-// in flight per thread before their stores.
-// NORM: what lands in LDS is the unit map, (x - mu) * s with the (mu, s) pair k_gm_stats left for the element's channel in
-// `stats` (pair 0: channel 0 of the range in this sample), fetched once per channel row of the call: a 16-byte-path thread holds
-// four rows, a dword-path wave one row at a time, so there the pair is wave-uniform and read as such. The product is rounded
-// once and +0.0 is added to it: a flat map (s = 0) becomes +0.0 in every element whatever the sign of x - mu, and no other
-// value changes. Out of range stays 0, not (0 - mu) * s, and no pair is read for a channel beyond the range.
-template <bool VEC, bool NORM>
-__device__ __forceinline__ void stage_tile(const float* __restrict__ base, long long strideC, int count, int ch0, int hw, int p0,
-                                           float* __restrict__ lds, const float2* __restrict__ stats) {
-  constexpr int PER = VEC ? KP / 4 : KP;     // threads per channel row
-  constexpr int ROWS = THREADS / PER;        // channel rows per step
-  constexpr int E = VEC ? 4 : 1;
-  const int c = threadIdx.x / PER, e = E * (threadIdx.x % PER), p = p0 + e;
-  const float* src = base + (long long)(ch0 + c) * strideC + p;
-  float* dst = lds + c * LD + e;
-  const bool inside = p < hw;
-#pragma unroll 4
-  for (int i = 0; i < TS / ROWS; ++i) {
-    const bool ok = inside && ch0 + c + ROWS * i < count;
-    const float* s = src + (long long)(ROWS * i) * strideC;
-    if constexpr (!NORM) {
-      if constexpr (VEC)
-        *reinterpret_cast<float4*>(dst + ROWS * i * LD) = ok ? *reinterpret_cast<const float4*>(s) : float4{0.f, 0.f, 0.f, 0.f};
-      else
-        dst[ROWS * i * LD] = ok ? *s : 0.f;
-    } else {
-      const int ch = ch0 + ROWS * i + (VEC ? c : __builtin_amdgcn_readfirstlane(c));  // PER == 64: a wave is one channel row
-      const float2 ms = ch < count ? stats[ch] : float2{0.f, 0.f};
-      if constexpr (VEC) {
-        float4 v{0.f, 0.f, 0.f, 0.f};
-        if (ok) {
-          const float4 t = *reinterpret_cast<const float4*>(s);
-          v = float4{unit(t.x, ms), unit(t.y, ms), unit(t.z, ms), unit(t.w, ms)};
-        }
-        *reinterpret_cast<float4*>(dst + ROWS * i * LD) = v;
-      } else {
-        dst[ROWS * i * LD] = ok ? unit(*s, ms) : 0.f;
-      }
-    }
-  }
-}
-
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-// two consecutive elements of a pair at once: v_pk_add_f32 (with the negation as a source modifier), v_pk_fma_f32
-__device__ __forceinline__ void pair_step(v2f a, v2f b, v2f& acc) {
-  const v2f d = a - b;
-  acc = __builtin_elementwise_fma(d, d, acc);
-}
 
 // NORM: the distance between the unit maps; sa / sb: the (mu, s) pairs of the scored and of the reference range, [N][c_count]
 // and [N][r_count] (k_gm_stats). Without NORM they are not read.
@@ -253,11 +195,21 @@ namespace dctsi {
 int dispatch_gm(const GmGeom& g, float* out, hipStream_t st) {
   const long long blocks = g.N * ((g.c_count + TS - 1) / TS);  // one workgroup per sample and scored tile: no grid loop
   if (blocks > kGmMaxBlocks) return DCTS_E_SHAPE;
-  const bool vec = (reinterpret_cast<uintptr_t>(g.x) & 15) == 0 && g.strideN % 4 == 0 && g.strideC % 4 == 0 && g.hw % 4 == 0;
-  if (vec)
+  if (gm_vec(g))
     hipLaunchKernelGGL((k_gm_distance<true, false>), dim3((unsigned)blocks), dim3(THREADS), 0, st, g, out, nullptr, nullptr);
   else
     hipLaunchKernelGGL((k_gm_distance<false, false>), dim3((unsigned)blocks), dim3(THREADS), 0, st, g, out, nullptr, nullptr);
+  return (int)hipGetLastError();
+}
+
+// One k_gm_stats launch: the (mu, s) pairs of channels [begin, begin + count) of every sample, [N][count] at `pairs`. The
+// caller has checked the grid against kGmMaxBlocks.
+int launch_gm_stats(const GmGeom& g, bool center, int begin, int count, float2* pairs, hipStream_t st) {
+  const bool vec = gm_vec(g);
+  const dim3 grid((unsigned)((g.N * count + kGmStatsMaps - 1) / kGmStatsMaps)), block(kGmStatsThreads);
+  const auto kernel = vec ? (center ? k_gm_stats<true, true> : k_gm_stats<true, false>)
+                          : (center ? k_gm_stats<false, true> : k_gm_stats<false, false>);
+  hipLaunchKernelGGL(kernel, grid, block, 0, st, g, begin, count, pairs);
   return (int)hipGetLastError();
 }
 
@@ -268,20 +220,12 @@ int dispatch_gm_metric(const GmGeom& g, bool center, float2* sa, float2* sb, flo
   const int larger = g.c_count > g.r_count ? g.c_count : g.r_count;
   const long long stats_blocks = (g.N * larger + kGmStatsMaps - 1) / kGmStatsMaps;
   if (blocks > kGmMaxBlocks || stats_blocks > kGmMaxBlocks) return DCTS_E_SHAPE;
-  const bool vec = (reinterpret_cast<uintptr_t>(g.x) & 15) == 0 && g.strideN % 4 == 0 && g.strideC % 4 == 0 && g.hw % 4 == 0;
-  auto stats = [&](int begin, int count, float2* pairs) {
-    const dim3 grid((unsigned)((g.N * count + kGmStatsMaps - 1) / kGmStatsMaps)), block(kGmStatsThreads);
-    const auto kernel = vec ? (center ? k_gm_stats<true, true> : k_gm_stats<true, false>)
-                            : (center ? k_gm_stats<false, true> : k_gm_stats<false, false>);
-    hipLaunchKernelGGL(kernel, grid, block, 0, st, g, begin, count, pairs);
-    return (int)hipGetLastError();
-  };
-  if (const int rc = stats(g.c_begin, g.c_count, sa)) return rc;
+  if (const int rc = launch_gm_stats(g, center, g.c_begin, g.c_count, sa, st)) return rc;
   if (g.r_begin == g.c_begin && g.r_count == g.c_count)
     sb = sa;
-  else if (const int rc = stats(g.r_begin, g.r_count, sb))
+  else if (const int rc = launch_gm_stats(g, center, g.r_begin, g.r_count, sb, st))
     return rc;
-  if (vec)
+  if (gm_vec(g))
     hipLaunchKernelGGL((k_gm_distance<true, true>), dim3((unsigned)blocks), dim3(THREADS), 0, st, g, out, sa, sb);
   else
     hipLaunchKernelGGL((k_gm_distance<false, true>), dim3((unsigned)blocks), dim3(THREADS), 0, st, g, out, sa, sb);

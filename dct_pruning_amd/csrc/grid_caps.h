@@ -81,6 +81,28 @@ constexpr long long kGmMaxBlocks = 0x7fffffffLL;
 // = kGmStatsMaps waves, one workgroup per kGmStatsMaps maps and no grid-stride loop either: the same largest grid, the same refusal
 constexpr int kGmStatsThreads = 256;
 constexpr int kGmStatsMaps = kGmStatsThreads / 64;
+// gm_pairs.hip, k_gm_pairs: a workgroup of kGmThreads threads owns kGmTS scored channels, kGmTR reference channels and one
+// slice of the samples; with more than one slice k_gm_pairs_sum (one thread per entry, workgroups of kGmPairSumThreads) adds
+// the slices' partial matrices. Both grids are exact and capped by kGmMaxBlocks as well.
+// The slices: enough of them that a square layer launches about kGmPairTarget workgroups (sixteen per CU of an MI355X: four
+// rounds of the four that are resident; measured against 1024 and 2048), never more than there are samples, every slice the same ceil(N / S) samples but the last, none empty. A function of N and r_count
+// alone: a call on a sub-range of the scored channels cuts the samples as the call on the whole range does, and the partial
+// matrices of a square layer stay within kGmPairTarget * 64 * 64 * 4 bytes = 64 MiB. DCTS_GM_PAIRS_ONE_SLICE is a development
+// define: the measurement of the rule against no slicing.
+constexpr int kGmPairTarget = 4096;
+constexpr int kGmPairSumThreads = 256;
+inline int gm_pair_slices(long long N, int r_count) {
+  if (N <= 0 || r_count <= 0) return 0;
+#ifdef DCTS_GM_PAIRS_ONE_SLICE
+  return 1;
+#else
+  const long long rt = (r_count + kGmTR - 1) / kGmTR;
+  long long s = kGmPairTarget / (rt * rt);
+  s = s < 1 ? 1 : (s > N ? N : s);
+  const long long per = (N + s - 1) / s;  // samples per slice
+  return (int)((N + per - 1) / per);      // the slices that hold a sample
+#endif
+}
 
 // nhwc.hip: waves per workgroup of the lane = channel kernel (a wave takes 64 channels of one sample), and the channels a
 // workgroup of the block kernel (edges 14 ... 32) and of the strip kernel (edge 56) takes

@@ -45,7 +45,16 @@ Additions (opt-in, results identical on fixed batches):
                       (x / |x|, or (x - mean) / |x - mean|: ops.gm_distance_nc(metric=...)), so that a channel's gain, which
                       BatchNorm sets per channel, does not count as distance and a scaled copy of a map is a duplicate; flat
                       (dead) maps land at the low end with the duplicates. Those files go to
-                      gm_score/<net>_limit<L>_<metric>/gm_*.npy;
+                      gm_score/<net>_limit<L>_<metric>/gm_*.npy. gm_pairs=True keeps the terms instead of their sum
+                      (dcts_gm_pairs_f32, ops.gm_pair_matrix): a [c, c] matrix per file, the mean over the samples of the
+                      distance between every two of the channels that compete for that file's mask (all C for "full" and
+                      "input", the last 12 for "last12", the block [lo:hi, lo:hi] for a file that is a channel slice of its
+                      hook point), in gm_score/<net>_limit<L>[_<metric>]_pairs/gm_*.npy. A row sum cannot tell two
+                      duplicates that are far from everything else from two distinct maps; the matrix can, and
+                      dct_pruning_amd.pairs turns it into imp_*.npy under a selection rule (row sum, nearest neighbour,
+                      farthest point) afterwards, on the host, as bands.collapse does for a spectrum. Its value is the fp32
+                      sum of the batch matrices in batch order divided once by the number of samples
+                      (accumulate.PairAccumulator), in every schedule and for every world size;
   autocast="fp16" | "bf16"
                       the forward sweeps run under torch.autocast; the hooks hand the tensors to ops.energy_nc in
                       whatever dtype arrives (float16 / bfloat16 maps are scored natively, dcts_energy_typed; a tensor
@@ -70,7 +79,7 @@ import torch
 
 from . import bands as _bands
 from . import ops, schedules, sharding
-from .accumulate import DeviceAccumulator, DeviceBatchAccumulator, HostAccumulator
+from .accumulate import DeviceAccumulator, DeviceBatchAccumulator, HostAccumulator, PairAccumulator
 
 # tests swap these for the oracle to exercise the host logic without a GPU
 _energy_nc = ops.energy_nc
@@ -78,6 +87,7 @@ _rank_nc = ops.rank_nc
 _band_energy_nc = ops.band_energy_nc
 _entropy_nc = ops.spectral_entropy_nc
 _gm_nc = ops.gm_distance_nc
+_gm_pairs_nc = ops.gm_pair_matrix
 
 AUTOCAST = {"fp16": torch.float16, "bf16": torch.bfloat16}
 
@@ -124,6 +134,13 @@ def _score_gm(x, c_begin, c_count, pad, ref):
     not the default's: "l2" is the call it always was."""
     kw = {} if _gm_metric == "l2" else {"metric": _gm_metric}
     return _gm_nc(x, c_begin=c_begin, c_count=c_count, ref_begin=ref[0], ref_count=ref[1], **kw)
+
+
+def _pair_matrix(x, c_begin, c_count, ref):
+    """gm's option gm_pairs: the [c_count, ref[1]] distances of a channel range to the maps of `ref`, summed over the samples
+    of x. The metric is named as _score_gm names it."""
+    kw = {} if _gm_metric == "l2" else {"metric": _gm_metric}
+    return _gm_pairs_nc(x, c_begin=c_begin, c_count=c_count, ref_begin=ref[0], ref_count=ref[1], **kw)
 
 
 # A criterion is its scorer above and its row here; everything below reads the row.
@@ -318,9 +335,10 @@ def _file_stem(criterion, stem):
     return prefix + (stem[len("imp_"):] if stem.startswith("imp_") else stem)
 
 
-def _save(out_dir, net_name, pt, scores, criterion="dct"):
+def _save(out_dir, net_name, pt, scores, criterion="dct", pairs=False):
+    """pairs: `scores` is the hook point's [C, C] pair matrix and a file that is a channel slice gets its diagonal block."""
     for stem, lo, hi in pt.files:
-        arr = scores if lo is None else scores[lo:hi]
+        arr = scores if lo is None else (scores[lo:hi, lo:hi] if pairs else scores[lo:hi])
         np.save(os.path.join(out_dir, _file_stem(criterion, stem) + ".npy"), arr)
         line = _done_line(net_name, 0, stem)
         if line:
@@ -335,15 +353,21 @@ class _PointHook:
     scored channels that THIS rank owns (sharding.make_units cuts wide layers so that eight ranks balance);
     None = the whole hook point under `key`. Per-channel scores do not depend on which call computes them,
     so the pieces concatenate to the unsplit result bit for bit (a cross-channel criterion's pieces are all scored against
-    the hook kind's whole channel set)."""
+    the hook kind's whole channel set).
+
+    `pairs` (the gm criterion's gm_pairs): every piece is a [c, C] pair matrix, rows [lo, hi) against the hook kind's whole
+    channel set, in a PairAccumulator of its own (host or device form, by `accumulate`; `batch` is not used)."""
 
     def __init__(self, kind, accumulate, device, batch=None, key=None, deferred=False, ranges=None, nominal_c=None,
-                 criterion="dct"):
+                 criterion="dct", pairs=False):
         self.kind, self.accumulate, self.device, self.acc = kind, accumulate, device, None
         self.crit = _TABLE[criterion]
         self.batch, self.key, self.deferred = batch, key, deferred
         self.ranges, self.nominal_c, self.accs = ranges, nominal_c, {}
         self.width = None  # K of the band criterion: scores come back as [c, K]
+        self.pairs = pairs
+        if pairs and not self.crit.cross:
+            raise ValueError("pair matrices go with a cross-channel criterion, not with %r" % criterion)
 
     def _pieces(self, x):
         """(key, c_begin, c_count, pad_front_if_odd) of every operator call this hook makes on x."""
@@ -361,6 +385,13 @@ class _PointHook:
         x = _scored_tensor(self.kind, inputs, output)
         ref = _kind_slice(self.crit, self.kind, x.shape[1])[:2]
         for key, cb, cc, pad in self._pieces(x):
+            if self.pairs:
+                m = _pair_matrix(x, cb, cc, ref)
+                acc = self.accs.get(key)
+                if acc is None:
+                    acc = self.accs[key] = PairAccumulator(m.device if self.accumulate == "device" else None)
+                acc.update(m, x.shape[0])
+                continue
             if self.deferred and self.batch is not None:
                 self.batch.add_tensor(key, x, cb, cc, pad)
                 continue
@@ -379,6 +410,8 @@ class _PointHook:
 
     def scores(self, key=None):
         key = self.key if key is None else key
+        if self.pairs:
+            return np.ascontiguousarray(self.accs[key].scores(), dtype=np.float32)
         if self.batch is not None:
             flat = np.ascontiguousarray(self.batch.scores(key), dtype=np.float32)
         else:
@@ -404,7 +437,8 @@ class _ChannelsLastLoader:
             yield data.contiguous(memory_format=torch.channels_last), target
 
 
-def check_options(criterion, net, deferred=False, autocast=None, channels_last=False, bands=(4, "square"), gm_metric="l2"):
+def check_options(criterion, net, deferred=False, autocast=None, channels_last=False, bands=(4, "square"), gm_metric="l2",
+                  gm_pairs=False):
     """Raises the ValueError of the first rule an imp_score call with these options breaks: what the criterion's row
     supports, and the two rules that hold for every criterion (autocast and channels_last have no deferred mode,
     channels_last does not cover u2netp). importance_generation.py's parser rejects its command lines with it."""
@@ -416,6 +450,8 @@ def check_options(criterion, net, deferred=False, autocast=None, channels_last=F
             raise ValueError("imp_score: gm_metric must be one of %s, got %r" % (", ".join(crit.metrics), gm_metric))
         raise ValueError("imp_score: gm_metric=%r goes with criterion='gm' only (the %s criterion compares no maps)"
                          % (gm_metric, criterion))
+    if gm_pairs and not crit.cross:
+        raise ValueError("imp_score: gm_pairs goes with criterion='gm' only (the %s criterion compares no maps)" % criterion)
     if autocast is not None:
         if autocast not in AUTOCAST:
             raise ValueError("imp_score: autocast must be None, 'fp16' or 'bf16', got %r" % (autocast,))
@@ -444,7 +480,7 @@ def check_options(criterion, net, deferred=False, autocast=None, channels_last=F
 
 
 def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host", group=None, deferred=False,
-              criterion="dct", bands=(4, "square"), autocast=None, channels_last=False, gm_metric="l2"):
+              criterion="dct", bands=(4, "square"), autocast=None, channels_last=False, gm_metric="l2", gm_pairs=False):
     """Counterpart of utils/common.py:367-977. `args` needs .net, .limit (and whatever
     load_data reads when train_loader is None). criterion="rank" scores HRank's feature-map rank instead of the
     DCT energy and writes rank_conv/<net>_limit<L>/rank_*.npy. criterion="bands" with bands=(K, kind) writes the
@@ -453,13 +489,14 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
     seven nets; not with deferred, autocast or channels_last). criterion="gm" scores every map's summed distance to the
     maps of its hook's channels and writes gm_score/<net>_limit<L>/gm_*.npy (all seven nets; same exclusions); with
     gm_metric="cosine" / "correlation" the distance is taken between unit maps and the files go to
-    gm_score/<net>_limit<L>_<metric>/ (criterion "gm" only).
+    gm_score/<net>_limit<L>_<metric>/ (criterion "gm" only). gm_pairs=True (criterion "gm" only) writes the [c, c] matrix of
+    mean pair distances per file instead, to gm_score/<net>_limit<L>[_<metric>]_pairs/, for dct_pruning_amd.pairs to score.
     autocast="fp16" / "bf16" runs the forward sweeps under torch.autocast and scores the half-precision tensors the
     hooks then see as they are (criterion "dct" only, not with deferred).
     channels_last=True converts the net (in place) and every input batch to torch.channels_last; the tensors the hooks
     then see are scored in the layout they arrive in (criterion "dct" only, not with deferred, not u2netp)."""
     global _acc, _band_cfg, _gm_metric
-    check_options(criterion, args.net, deferred, autocast, channels_last, bands, gm_metric)
+    check_options(criterion, args.net, deferred, autocast, channels_last, bands, gm_metric, gm_pairs)
     _gm_metric = gm_metric
     crit = _TABLE[criterion]
     if not hasattr(args, "limit"):
@@ -475,6 +512,8 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
         out_dir += "_%s%d" % (_band_cfg[1], width)
     if gm_metric != "l2":
         out_dir += "_" + gm_metric
+    if gm_pairs:
+        out_dir += "_pairs"
     world, rank = 1, 0
     if group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
         world = torch.distributed.get_world_size(group)
@@ -544,7 +583,7 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
             whole = per_layer[i] == 1
             hooks[i] = _PointHook(pts[i].kind, accumulate, dev, batch=batch, key=ks[0], deferred=deferred,
                                   ranges=None if whole else [(k, units[k].c_lo, units[k].c_hi) for k in ks],
-                                  nominal_c=chans[i], criterion=criterion)
+                                  nominal_c=chans[i], criterion=criterion, pairs=gm_pairs)
             handles.append(_resolve(net, pts[i].module).register_forward_hook(hooks[i]))
         sweep(net, train_loader, args.limit)
         for h in handles:
@@ -559,8 +598,8 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
             if args.net == "u2netp" and world == 1:
                 print("current layer:", "net." + pt.module)
             layer = _resolve(net, pt.module)
-            if accumulate == "device":
-                hook = _PointHook(pt.kind, accumulate, dev, key=k, criterion=criterion)
+            if accumulate == "device" or gm_pairs:  # the pair matrices have no module-level hook: _PointHook in both forms
+                hook = _PointHook(pt.kind, accumulate, dev, key=k, criterion=criterion, pairs=gm_pairs)
                 handler = layer.register_forward_hook(hook)
                 sweep(net, train_loader, args.limit)
                 handler.remove()
@@ -574,20 +613,23 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
                     results[k] = results[k].reshape(-1, width)
                 _acc.reset()
             if world == 1:
-                _save(out_dir, args.net, pt, results[k], criterion)
+                _save(out_dir, args.net, pt, results[k], criterion, gm_pairs)
         if world == 1:
             print("The importance score generation has been completed!")  # utils/common.py:977
             return
 
     if world > 1:
-        layer_scores = _gather_results(results, units, len(pts), owner, world, rank, dev, group, width=width)
+        # floats per channel of a layer's score: the criterion's width, or the layer's own channel count for a pair matrix
+        # (None: as wide as the owners' results say, which also holds for a net pruned below the schedule's widths)
+        layer_scores = _gather_results(results, units, len(pts), owner, world, rank, dev, group,
+                                       width=[None] * len(pts) if gm_pairs else width)
     else:
         layer_scores = {units[k].layer: results[k] for k in mine}
     if rank == 0:
         for i, pt in enumerate(pts):
             if args.net == "u2netp":
                 print("current layer:", "net." + pt.module)
-            _save(out_dir, args.net, pt, layer_scores[i], criterion)
+            _save(out_dir, args.net, pt, layer_scores[i], criterion, gm_pairs)
         print("The importance score generation has been completed!")
     if world > 1:
         torch.distributed.barrier(group)
@@ -596,16 +638,27 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
 def _gather_results(local, units, n_layers, owner, world, rank, dev, group, width=1):
     """One all-gather of the flat, equally padded score buffer (plus a tiny all-reduce that tells every rank
     the channel counts of the units, which only their owners know for certain: imp_score also runs on
-    already-pruned nets whose widths differ from the schedule's). Returns {layer: (C,) scores}. width > 1 (the band
-    criterion's K): a unit of c channels carries c * width floats and the scores come back as (C, width)."""
+    already-pruned nets whose widths differ from the schedule's). Returns {layer: (C,) scores}.
+    width: the floats a channel of a score carries, one number for every layer or one per layer: 1 gives (C,) scores; K > 1
+    (the band criterion's K; a pair matrix's row length) means a unit of c channels carries c * K floats and the layer's
+    scores come back as (C, K). None for a layer: whatever the owners of its units report (the all-reduce carries the row
+    lengths as well), which must agree among them."""
     import torch.distributed as dist
     backend = dist.get_backend(group)
     cdev = dev if backend == "nccl" else torch.device("cpu")
-    counts = torch.zeros(len(units), dtype=torch.int64, device=cdev)
+    widths = list(width) if isinstance(width, (list, tuple)) else [width] * n_layers
+    counts = torch.zeros(2, len(units), dtype=torch.int64, device=cdev)  # channels; floats per channel
     for k, v in local.items():
-        counts[k] = v.shape[0]
+        counts[0, k] = v.shape[0]
+        counts[1, k] = v.shape[1] if v.ndim == 2 else 1
     dist.all_reduce(counts, group=group)
-    counts = counts.cpu().tolist()
+    counts, rows = counts.cpu().tolist()
+    for k, u in enumerate(units):
+        if widths[u.layer] is None:
+            widths[u.layer] = rows[k]
+        if rows[k] != widths[u.layer]:
+            raise RuntimeError("unit %d of hook point %d came back with %d floats per channel, expected %d"
+                               % (k, u.layer, rows[k], widths[u.layer]))
     # actual units: a whole hook point spans [0, actual C); a channel range keeps its bounds
     per_layer = [0] * n_layers
     for u in units:
@@ -622,15 +675,15 @@ def _gather_results(local, units, n_layers, owner, world, rank, dev, group, widt
     chans = [0] * n_layers
     for u in real:
         chans[u.layer] = max(chans[u.layer], u.c_hi)
-    if width > 1:
-        real = [sharding.Unit(u.layer, u.c_lo * width, u.c_hi * width, u.cost) for u in real]
-        chans = [c * width for c in chans]
+    # in floats: a unit of channels [lo, hi) of a layer of width w is the floats [lo * w, hi * w) of the layer's flat scores
+    real = [sharding.Unit(u.layer, u.c_lo * widths[u.layer], u.c_hi * widths[u.layer], u.cost) for u in real]
+    chans = [c * w for c, w in zip(chans, widths)]
     off, seg = sharding.layout(real, owner, world)
     flat = torch.zeros(seg, dtype=torch.float32, device=cdev)
     for k, v in local.items():
-        flat[off[k]:off[k] + counts[k] * width] = torch.from_numpy(v.reshape(-1)).to(cdev)
+        flat[off[k]:off[k] + v.size] = torch.from_numpy(v.reshape(-1)).to(cdev)
     gathered = sharding.all_gather_scores(flat, world, group)
     res = sharding.unpack(gathered, real, owner, off, chans)
-    if width > 1:
-        return {i: r.cpu().numpy().reshape(-1, width) for i, r in enumerate(res)}
-    return {i: r.cpu().numpy() for i, r in enumerate(res)}
+    # a layer whose width was given as 1 keeps its (C,) shape; one that was given K > 1 or learned its width is (C, K)
+    given = list(width) if isinstance(width, (list, tuple)) else [width] * n_layers
+    return {i: r.cpu().numpy() if given[i] == 1 else r.cpu().numpy().reshape(-1, widths[i]) for i, r in enumerate(res)}

@@ -57,9 +57,11 @@ class BandWeightsError(ValueError):
     """A [C, K] band spectrum met without band weights, or with the wrong number of them."""
 
 
-def masks_for_dir(score_dir, rates, band_weights=None):
+def masks_for_dir(score_dir, rates, band_weights=None, pair_rule=None):
     """{file stem: kept indices (int64, sorted)}; `rates` is a float or a list in natural file order. A 2-D score file
-    (a [C, K] band spectrum of imp_score(criterion="bands")) needs `band_weights` (K numbers): imp = file @ weights."""
+    (a [C, K] band spectrum of imp_score(criterion="bands")) needs `band_weights` (K numbers): imp = file @ weights.
+    With `pair_rule` ("sum", "nn", "kcenter") a 2-D file is a [C, C] pair matrix of imp_score(criterion="gm", gm_pairs=True)
+    instead: imp = pairs.score(file, pair_rule), under the stem `python -m dct_pruning_amd.pairs` would write it to."""
     files = score_files(score_dir)
     if isinstance(rates, (int, float)):
         rates = [float(rates)] * len(files)
@@ -68,7 +70,16 @@ def masks_for_dir(score_dir, rates, band_weights=None):
     out = {}
     for f, r in zip(files, rates):
         imp = np.load(os.path.join(score_dir, f), allow_pickle=False)
-        if imp.ndim == 2:
+        stem = f[:-4]
+        if imp.ndim == 2 and pair_rule is not None:
+            from . import pairs
+            try:
+                imp = pairs.score(imp, pair_rule)
+            except ValueError as exc:
+                raise BandWeightsError("%s: %s" % (f, exc))
+            if f.startswith("gm_"):
+                stem = pairs.score_file_name(f)[:-4]
+        elif imp.ndim == 2:
             if band_weights is None:
                 raise BandWeightsError("%s holds a [%d, %d] band spectrum: give --band_weights w0,w1,... (one per band) to "
                                  "turn it into scores" % (f, imp.shape[0], imp.shape[1]))
@@ -78,7 +89,7 @@ def masks_for_dir(score_dir, rates, band_weights=None):
             except ValueError as exc:
                 raise BandWeightsError("%s: %s" % (f, exc))
         c = imp.shape[0]
-        out[f[:-4]] = select_index(imp, c, int(c * (1 - r)))
+        out[stem] = select_index(imp, c, int(c * (1 - r)))
     return out
 
 
@@ -97,6 +108,9 @@ def main(argv=None):
     ap.add_argument("--compare", default=None, help="second score directory: report whether the masks match")
     ap.add_argument("--band_weights", default=None,
                     help="for directories of [C, K] band spectra (band_*.npy): one weight per band, e.g. 1,0.5,0.25,0")
+    ap.add_argument("--pair_rule", default=None, choices=("sum", "nn", "kcenter"),
+                    help="for directories of [C, C] pair matrices (gm_*.npy of a --gm_pairs sweep): the selection rule of "
+                         "dct_pruning_amd.pairs that turns each into scores")
     args = ap.parse_args(argv)
     rates = parse_compress_rate(args.compress_rate)
     bw = None
@@ -107,7 +121,7 @@ def main(argv=None):
         except ValueError as exc:
             ap.error(str(exc))
     try:
-        masks = masks_for_dir(args.imp_score, rates, bw)
+        masks = masks_for_dir(args.imp_score, rates, bw, args.pair_rule)
     except BandWeightsError as exc:
         ap.error(str(exc))
     for k, v in masks.items():
@@ -115,7 +129,7 @@ def main(argv=None):
     if args.out:
         np.savez(args.out, **masks)
     if args.compare:
-        bad = compare(masks, masks_for_dir(args.compare, rates, bw))
+        bad = compare(masks, masks_for_dir(args.compare, rates, bw, args.pair_rule))
         print("masks identical" if not bad else "masks differ in: " + ", ".join(bad))
         return 1 if bad else 0
     return 0

@@ -382,3 +382,30 @@ def gm_distance_nc(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, out=
     ws = _workspace(x.device, stream, max(lib.dcts_gm_workspace_bytes(GM_METRICS[metric], N, c_count, ref_count), 16))
     _launch(x.device, lib.dcts_gm_distance_metric_f32, *args, GM_METRICS[metric], ws.data_ptr(), ws.numel())
     return out
+
+
+def gm_pair_matrix(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, metric="l2", out=None):
+    """D[j, k] = sum_n d(x[n, c_begin+j], x[n, ref_begin+k]) -> [c_count, ref_count] fp32 (ref_count None = to the end).
+
+    The pair matrix of the geometric-median criterion (dcts_gm_pairs_f32): the terms gm_distance_nc adds up over the reference
+    channels, every one kept and summed over the samples of the batch instead (a sum, not a mean: divide by x.shape[0]). d is
+    gm_distance_nc's distance under `metric`, with everything that is exact there: D[c, c] = +0.0, identical maps (under a metric,
+    power-of-two multiples) at +0.0, D[j, k] and D[k, j] of a square call the same bits, and the rows of a channel range scored
+    against the same reference set are the rows of the whole matrix bit for bit. Selection rules on it are host arithmetic
+    (dct_pruning_amd.pairs).
+    float32 NCHW only; a tensor whose maps are not dense is copied with .contiguous() first. `out`: a contiguous float32
+    [c_count, ref_count] tensor on x's device to overwrite. Enqueues on the current stream of x's device; no synchronisation."""
+    if metric not in GM_METRICS:
+        raise ValueError("metric must be one of %s, got %r" % (", ".join(GM_METRICS), metric))
+    x, c_begin, c_count, _, stream = _open(x, c_begin, c_count, out=False, rows="dense")
+    ref_begin, ref_count = _slice(x, ref_begin, ref_count)
+    if out is None:
+        out = torch.empty((c_count, ref_count), dtype=torch.float32, device=x.device)
+    elif (out.shape != (c_count, ref_count) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device):
+        raise ValueError("out must be a contiguous float32 [c_count, ref_count] tensor on x's device")
+    N, C, H, W = x.shape
+    lib = _lib.load()
+    ws = _workspace(x.device, stream, max(lib.dcts_gm_pairs_workspace_bytes(GM_METRICS[metric], N, c_count, ref_count), 16))
+    _launch(x.device, lib.dcts_gm_pairs_f32, x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+            c_begin, c_count, ref_begin, ref_count, out.data_ptr(), stream, GM_METRICS[metric], ws.data_ptr(), ws.numel())
+    return out

@@ -12,7 +12,9 @@ the DCT energy under importance_score/, HRank's feature-map rank under rank_conv
 per channel, --bands K --band_kind {square,diag}, under band_score/, the spectral entropy of the DCT coefficients
 under entropy_score/, or every map's summed distance to the other maps of its layer, the geometric-median criterion, under
 gm_score/; --gm_metric {l2,cosine,correlation} takes that distance between the maps as they are or between unit maps, which
-go to gm_score/<net>_limit<L>_<metric>/), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
+go to gm_score/<net>_limit<L>_<metric>/, and --gm_pairs writes the [c, c] matrix of mean pair distances per file instead of its
+row sums, to gm_score/<net>_limit<L>[_<metric>]_pairs/, which `python -m dct_pruning_amd.pairs --matrix DIR --rule
+{sum,nn,kcenter} --out DIR2` turns into imp_*.npy on the host), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
 half-precision feature maps are scored as they are) and --channels_last (the net and its inputs run in
 torch.channels_last and the feature maps are scored in the layout they arrive in). dct_pruning_amd/harness.py says
 what each criterion writes and which of these modes and nets it supports (its criterion table and check_options, which
@@ -60,6 +62,10 @@ def parse_args(argv=None):
                         help="--criterion gm: l2 compares the maps as they are; cosine (x / |x|) and correlation "
                              "((x - mean) / |x - mean|) compare unit maps, so a channel's gain is no distance and a scaled "
                              "copy is a duplicate (gm_score/<net>_limit<L>_<metric>/)")
+    parser.add_argument("--gm_pairs", action="store_true",
+                        help="--criterion gm: write the [c, c] matrix of mean pair distances per file instead of its row sums "
+                             "(gm_score/<net>_limit<L>[_<metric>]_pairs/); python -m dct_pruning_amd.pairs turns it into "
+                             "imp_*.npy under a selection rule (sum, nn, kcenter)")
     parser.add_argument("--autocast", type=str, default=None, choices=("fp16", "bf16"),
                         help="run the forward sweeps under torch.autocast and score the half-precision feature maps natively")
     parser.add_argument("--channels_last", action="store_true",
@@ -67,7 +73,7 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     try:
         harness.check_options(args.criterion, args.net, args.deferred, args.autocast, args.channels_last,
-                              (args.bands, args.band_kind), gm_metric=args.gm_metric)
+                              (args.bands, args.band_kind), gm_metric=args.gm_metric, gm_pairs=args.gm_pairs)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -123,7 +129,7 @@ def main(argv=None):
     harness.imp_score(net, args, single_sweep=args.single_sweep,
                       accumulate="device" if args.device_accumulate else "host", deferred=args.deferred,
                       criterion=args.criterion, bands=(args.bands, args.band_kind), autocast=args.autocast,
-                      channels_last=args.channels_last, gm_metric=args.gm_metric)
+                      channels_last=args.channels_last, gm_metric=args.gm_metric, gm_pairs=args.gm_pairs)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -50,7 +50,8 @@ extern "C" {
  *    (dcts_energy_nhwc, dcts_nhwc_workspace_bytes, dcts_has_nhwc_kernel), and for the spectral-entropy ones
  *    (dcts_spectral_entropy_f32, dcts_entropy_workspace_bytes, dcts_has_entropy_kernel), and for the geometric-median
  *    criterion's entry point (dcts_gm_distance_f32) and its normalised metrics (dcts_gm_distance_metric_f32,
- *    dcts_gm_workspace_bytes, DCTS_GM_*). */
+ *    dcts_gm_workspace_bytes, DCTS_GM_*) and its pair matrix (dcts_gm_pairs_f32, dcts_gm_pairs_workspace_bytes,
+ *    dcts_gm_pairs_slices). */
 #define DCTS_ABI_VERSION 3
 
 enum {
@@ -324,6 +325,43 @@ int dcts_gm_distance_metric_f32(const float* x, int64_t N, int64_t C_total, int6
                                 int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
                                 int32_t c_begin, int32_t c_count, int32_t r_begin, int32_t r_count,
                                 float* out_nc, void* stream, int32_t metric, void* workspace, size_t workspace_bytes);
+
+/*
+ * The terms of dcts_gm_distance_metric_f32 instead of their sum over the reference set, summed over the SAMPLES (gm_pairs.hip):
+ *
+ *     out_cr[j*r_count + k] = sum_{n = 0}^{N-1} d(x[n, c_begin+j], x[n, r_begin+k])        [c_count, r_count] fp32, dense
+ *
+ * d the distance of dcts_gm_distance_metric_f32 under `metric` (DCTS_GM_L2: the maps as they are; DCTS_GM_COSINE,
+ * DCTS_GM_CORRELATION: their unit maps, flat maps as described there). A row sum cannot tell two duplicates that are far from
+ * everything else from two distinct far maps; the matrix can, and every selection rule on it (nearest neighbour, farthest
+ * point, clustering) is host arithmetic. It is a SUM over the samples, not a mean: the caller owns the count. One matrix per
+ * sample is not offered: [N, C, C] floats are 4 GiB for 2048 channels at batch 256. The call overwrites out_cr.
+ *   x, strides, the two channel ranges, metric     as for dcts_gm_distance_metric_f32.
+ *   Slices     the samples are cut into S = dcts_gm_pairs_slices(N, r_count) contiguous runs of ceil(N / S) samples (the last
+ *              one shorter, none empty), each summed with n ascending by a workgroup of its own so that a narrow layer still
+ *              fills the GPU; the S partial matrices are then added with s ascending. 1 <= S <= N; S depends on N and r_count
+ *              alone (0 for N <= 0 or r_count <= 0): not on the scored range, the alignment of x or the device.
+ *   workspace  device memory, 16-byte aligned, at least dcts_gm_pairs_workspace_bytes(metric, N, c_count, r_count) bytes: the
+ *              (mu, 1 / norm) pairs of a metric, laid out as dcts_gm_distance_metric_f32 has them, then the S partial matrices
+ *              where S > 1. 0 for DCTS_GM_L2 with S == 1, where NULL / 0 are fine and the one launch stores to out_cr itself.
+ *              The query returns 0 for a metric it does not know. Handled as the other entry points' workspace.
+ *   Checks, in this order: everything dcts_gm_distance_f32 checks, in its order (out_cr in the place of out_nc); the metric
+ *              (DCTS_E_UNSUPPORTED); the workspace (NULL or too small: DCTS_E_WORKSPACE; not 16-byte aligned: DCTS_E_ALIGN);
+ *              then the grids: a launch of more than 2^31 - 1 workgroups returns DCTS_E_SHAPE before anything is enqueued.
+ * Arithmetic: every pair exactly as in dcts_gm_distance_f32 / dcts_gm_distance_metric_f32 (the difference form, two fused
+ * multiply-add chains with p ascending, sqrtf), then fp32 additions in the order above. Hence, bit for bit: the entry of a
+ * channel with itself is +0.0; two identical maps are at +0.0 (under a metric, a map and a power-of-two multiple of it);
+ * an all-zero tensor gives +0.0 everywhere; with the scored range equal to the reference range out[j, k] has the bits of
+ * out[k, j]; a row of a call on a sub-range of the scored channels has the bits it has in the call on the whole range with the
+ * same reference range; the bits do not depend on the alignment of x. A NaN / Inf map reaches its own row and column only.
+ * Only enqueues on `stream`: two to four launches at most, no allocation, no atomics; the arguments are checked first.
+ */
+size_t dcts_gm_pairs_workspace_bytes(int32_t metric, int64_t N, int32_t c_count, int32_t r_count);
+int32_t dcts_gm_pairs_slices(int64_t N, int32_t r_count);
+int dcts_gm_pairs_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                      int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
+                      int32_t c_begin, int32_t c_count, int32_t r_begin, int32_t r_count,
+                      float* out_cr, void* stream, int32_t metric, void* workspace, size_t workspace_bytes);
 
 /*
  * dcts_energy_f32 for feature maps of another element type: what a forward pass under autocast hands to a hook.

@@ -11,7 +11,12 @@ as a share of the 157.3e12 of the MI355X's fp32 vector peak. That peak counts a 
 multiply and add): one operation (a subtract or an fma) per lane and clock is 39.3e12 per second at 2.4 GHz, a share of 0.25.
 --metric cosine | correlation times the normalised call (dcts_gm_distance_metric_f32): the stats launch that reads every map
 twice and the distance kernel that stages unit maps; pair_elems and the shares count the distance kernel's arithmetic alone.
-usage: tools/microbench_gm.py [--reps R] [--metric M] [N,C,H,W ...]"""
+--pairs times the pair-matrix call (dcts_gm_pairs_f32, gm_pairs.hip: the same inner loop, every distance kept and summed over
+the samples) and, alternating with it call by call in the same session, the row-sum call on the same tensor; one JSON line
+per shape holds both medians and their ratio. The pair-matrix call's launches (the stats of a metric, the kernel, the sum over
+the slices where there are several) are all inside its event pair. --lib PATH loads another build of the library, e.g. one
+compiled with -DDCTS_GM_PAIRS_ONE_SLICE, to measure the slice rule against no slicing.
+usage: tools/microbench_gm.py [--reps R] [--metric M] [--pairs] [--lib PATH] [N,C,H,W ...]"""
 import argparse
 import json
 import os
@@ -54,11 +59,56 @@ def run(shape, reps, metric):
     print(json.dumps(res), flush=True)
 
 
+def _timed(fn):
+    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    z.record()
+    return a, z
+
+
+def run_pairs(shape, reps, metric):
+    from dct_pruning_amd import _lib
+    n, c, h, w = shape
+    x = torch.relu(torch.randn(n, c, h, w, device="cuda"))
+    out, mat = torch.empty(n, c, device="cuda"), torch.empty(c, c, device="cuda")
+    calls = {"pairs": lambda: dpa.gm_pair_matrix(x, metric=metric, out=mat), "rows": lambda: dpa.gm_distance_nc(x, out=out, metric=metric)}
+    for _ in range(WARMUP):
+        for fn in calls.values():
+            fn()
+    torch.cuda.synchronize()
+    events = {k: [] for k in calls}
+    for _ in range(reps):  # alternating: both see the same clocks and the same neighbours
+        for k, fn in calls.items():
+            events[k].append(_timed(fn))
+    torch.cuda.synchronize()
+    med, lo, hi = {}, {}, {}
+    for k, ev in events.items():
+        ts = sorted(a.elapsed_time(z) for a, z in ev)
+        med[k], lo[k], hi[k] = ts[len(ts) // 2], ts[0], ts[-1]
+    pair_elems = n * c * c * h * w
+    slices = _lib.load().dcts_gm_pairs_slices(n, c)
+    res = {"shape": list(shape), "metric": metric, "reps": reps, "slices": slices, "workgroups": slices * (-(-c // 64)) ** 2,
+           "rows_workgroups": n * -(-c // 64), "lib": os.path.basename(_lib.LIB_PATH),
+           "pairs_median_ms": round(med["pairs"], 3), "pairs_min_ms": round(lo["pairs"], 3), "pairs_max_ms": round(hi["pairs"], 3),
+           "rows_median_ms": round(med["rows"], 3), "rows_min_ms": round(lo["rows"], 3), "rows_max_ms": round(hi["rows"], 3),
+           "pair_elems": pair_elems, "pairs_pair_elems_per_s": round(pair_elems / med["pairs"] * 1e3, 1),
+           "rows_pair_elems_per_s": round(pair_elems / med["rows"] * 1e3, 1),
+           "pairs_rate_over_rows_rate": round(med["rows"] / med["pairs"], 4),
+           "pairs_share_of_fp32_vector_peak": round(2 * pair_elems / med["pairs"] * 1e3 / PEAK_FP32_VECTOR, 4)}
+    print(json.dumps(res), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=21)
     ap.add_argument("--metric", default="l2", choices=("l2", "cosine", "correlation"))
+    ap.add_argument("--pairs", action="store_true", help="time the pair-matrix call, alternating with the row-sum call")
+    ap.add_argument("--lib", default=None, help="another build of libdctscore.so to load")
     ap.add_argument("shapes", nargs="*")
     a = ap.parse_args()
+    if a.lib:
+        from dct_pruning_amd import _lib
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     for s in [tuple(int(v) for v in s.split(",")) for s in a.shapes] or SHAPES:
-        run(s, a.reps, a.metric)
+        (run_pairs if a.pairs else run)(s, a.reps, a.metric)
