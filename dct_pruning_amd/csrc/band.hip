@@ -2,9 +2,8 @@
 //   out[m][b] = sum_{u,v} weights[b][u][v] * c[u][v]^2,  c = dct_2d(map m, norm='ortho'),  b = 0 ... K-1.
 // With one-hot weights (dct_pruning_amd/bands.py) that is the energy of K frequency bands of every map.
 //
-//   k_band_codelet   the codelet kernel's schedule with the slab geometry, grid rule, fence and segmented reduction of
-//                    codelet_schedule.hpp: pass 1 lane = column, transpose through the wave's LDS slab (plain stores),
-//                    pass 2 lane = row u with the N coefficients of that row in registers. What this unit adds is the
+//   k_band_codelet   the two-pass schedule of codelet_schedule.hpp (its group loop, load and passes): a lane ends with the
+//                    N coefficients of row u of its map in registers. What this unit adds is the
 //                    epilogue: KB accumulators e[b] = fma(wt[b][u][l], w[l] * w[l], e[b]) instead of one, then
 //                    the segmented wave reduction once per band and K stores per map. KB = K rounded up to 1, 2, 4, 8;
 //                    the bands above K have zero weights and are not stored. A band's chain of FMAs and its reduction
@@ -77,69 +76,18 @@ template <int N, int PAD, int KB>
 __global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_band_codelet(MapGeom g, const float* __restrict__ T, int K,
                                                                            float* __restrict__ out) {
   using Cfg = CodeletCfg<N>;
-  constexpr int G = Cfg::G, S = Cfg::S, MAP_LDS = Cfg::MAP_LDS, WAVES = Cfg::WAVES;
-  constexpr int W = N - PAD;  // data row length == row stride (dense rows)
-  __shared__ float slab[WAVES][Cfg::WAVE_LDS];
-
+  __shared__ float slab[Cfg::WAVES][Cfg::WAVE_LDS];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   float* my = slab[wave];
-  const int g1 = lane / N, c = lane - g1 * N;  // square tile: (map, column) in pass 1, (map, row) in pass 2
-  const bool act = g1 < G;
+  DCTS_CODELET_LANE(N, lane)
 
-  const long long ngroups = (g.nmaps + G - 1) / G;
-  const long long wave_gid = (long long)blockIdx.x * WAVES + wave;
-  const long long nwaves = (long long)gridDim.x * WAVES;
-
-  for (long long grp = wave_gid; grp < ngroups; grp += nwaves) {
-    // ---- pass 1: column DCT-II, lane = column ---------------------------------------------------
-    const long long m1 = grp * G + g1;
+  const CodeletGroups walk = codelet_groups<N>(g.nmaps);
+  for (long long grp = walk.first; grp < walk.ngroups; grp += walk.step) {
+    const long long m1 = grp * Cfg::G + g1;
     const bool has = act && m1 < g.nmaps;
-    float xr[N];
-    if constexpr (PAD == 0) {
-      // lanes without a map load some valid map instead; their results are never stored
-      const float* p = map_base(g, has ? m1 : g.nmaps - 1) + (has ? c : 0);
-      dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-        constexpr int r = decltype(i)::value;
-        xr[r] = p[r * W];
-      });
-    } else {
-      if (has && c >= PAD) {
-        const float* p = map_base(g, m1) + (c - PAD);
-        dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-          constexpr int r = decltype(i)::value;
-          if constexpr (r < PAD)
-            xr[r] = 0.f;
-          else
-            xr[r] = p[(r - PAD) * W];
-        });
-      } else {
-        dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE { xr[decltype(i)::value] = 0.f; });
-      }
-    }
-    float y[N];
-    dcts::Dct2<N>::run(xr, y);
-    y[0] *= dcts::kInvSqrt2;
-    if (act) {
-      float* dst = my + g1 * MAP_LDS + c;
-      dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-        constexpr int kk = decltype(i)::value;
-        dst[kk * S] = y[kk];
-      });
-    }
-    wave_fence();
-
-    // ---- pass 2: row DCT-II, lane = row u ------------------------------------------------------
-    float z[N], w[N];
-    {
-      const float* src = my + (act ? g1 : 0) * MAP_LDS + (act ? c : 0) * S;
-      dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-        constexpr int cc = decltype(i)::value;
-        z[cc] = src[cc];
-      });
-    }
-    dcts::Dct2<N>::run(z, w);
-    w[0] *= dcts::kInvSqrt2;
+    DCTS_CODELET_LOAD(N, PAD, g, m1, c, has, xr)
+    DCTS_CODELET_PASSES(N, xr, w, my, g1, c, act)
     float e[KB];
     dcts::static_for<KB>([&](auto ib) DCTS_LAMBDA_INLINE { e[decltype(ib)::value] = 0.f; });
     // The table does not depend on the group, so the compiler would hoist every weight load out of the grid-stride
@@ -184,11 +132,10 @@ __global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_band_codelet(Ma
       e[b] = eb;
     });
     if (has && c == 0) {
-      constexpr float sc = float(4.0 / (double(N) * double(N)));
       float* o = out + m1 * K;
       dcts::static_for<KB>([&](auto ib) DCTS_LAMBDA_INLINE {
         constexpr int b = decltype(ib)::value;
-        if (b < K) o[b] = e[b] * sc;
+        if (b < K) o[b] = e[b] * Cfg::SCALE;
       });
     }
     wave_fence();
@@ -226,10 +173,7 @@ __global__ __launch_bounds__((64 * kReduceWaves)) void k_band_reduce(const float
 
 template <int N, int PAD, int KB>
 int launch_band(const MapGeom& g, const float* T, int K, float* out, hipStream_t st) {
-  using Cfg = CodeletCfg<N>;
-  const long long ngroups = (g.nmaps + Cfg::G - 1) / Cfg::G;
-  hipLaunchKernelGGL((k_band_codelet<N, PAD, KB>), dim3(codelet_grid<N>(ngroups)), dim3(64 * Cfg::WAVES), 0, st, g, T, K, out);
-  return (int)hipGetLastError();
+  return launch_codelet_grid<N>(k_band_codelet<N, PAD, KB>, g.nmaps, st, g, T, K, out);
 }
 
 template <int N, int PAD>
@@ -268,10 +212,8 @@ int dispatch_band(int HP, int pad, const MapGeom& g, const float* weights, int K
 
 int launch_band_reduce(const float* coeff, const float* weights, long long nmaps, int hw, int K, float* out,
                        hipStream_t st) {
-  long long blocks = (nmaps + kReduceWaves - 1) / kReduceWaves;  // one wave per map
-  if (blocks > kReduceMaxBlocks) blocks = kReduceMaxBlocks;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_band_reduce, dim3((unsigned)blocks), dim3(64 * kReduceWaves), 0, st, coeff, weights, nmaps, hw, K, out);
+  const unsigned blocks = grid_blocks(nmaps, kReduceWaves, kReduceMaxBlocks);  // one wave per map
+  hipLaunchKernelGGL(k_band_reduce, dim3(blocks), dim3(64 * kReduceWaves), 0, st, coeff, weights, nmaps, hw, K, out);
   return (int)hipGetLastError();
 }
 

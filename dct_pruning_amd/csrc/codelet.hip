@@ -15,7 +15,7 @@
 //                     squares are summed in-lane and then across the map's lanes with a
 //                     segmented wave shuffle reduction. HBM traffic = the algorithmic
 //                     4*H*W + 4 bytes per map; LDS traffic = one write + one read per
-//                     element.
+//                     element. codelet_schedule.hpp states the plain form of this schedule.
 //   k_energy_lane_multi  7 x 7 and 9 x 9 maps, one lane per map (see below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -51,9 +51,12 @@ __device__ __forceinline__ void lds_write_addtid4(unsigned base, float a, float 
       : "memory", "m0");
 }
 
-// one group of G maps: both passes, the LDS transpose and the reduction (see the header comment). Every caller passes
-// HP == WP (the dispatchers refuse anything else; rect.hip serves non-square tiles), so the pass-2 role (g2, k, act2) equals
-// the pass-1 role. The two-role form stays: folding it changes the instruction order of 90 of this unit's 149 kernels.
+// One group of G maps: both passes, the LDS transpose and the reduction. The plain form of this body is stated in
+// codelet_schedule.hpp (DCTS_CODELET_LOAD, _PASSES, _ENERGY), where band.hip, entropy.hip, half.hip and nhwc.hip
+// take it from. This text is kept apart because bench.py measures these kernels and it leaves the plain form in two places:
+// the ds_write_addtid stores at G == 1 (below), and two lane roles. Every caller passes HP == WP (the dispatchers refuse
+// anything else; rect.hip serves non-square tiles), so the pass-2 role (g2, k, act2) equals the pass-1 role; folding the two,
+// or calling the shared pieces, changes the instruction order of 55 to 90 of this unit's 149 kernels.
 template <int HP, int WP, int PAD, bool STORE_COEFF>
 __device__ __forceinline__ void codelet_group(const MapGeom& g, float* __restrict__ out, long long grp,
                                               float* my, int g1, int c, int g2, int k, bool act1, bool act2) {
@@ -317,29 +320,6 @@ __device__ __forceinline__ void lane_compute(const MapGeom& g, const LaneGroup& 
   }
 }
 
-template <int N>
-__device__ __forceinline__ float lane_energy(float (&v)[N * N]) {
-  dcts::static_for<N>([&](auto ic) DCTS_LAMBDA_INLINE {  // columns, in place
-    constexpr int c = decltype(ic)::value;
-    float in[N], o[N];
-    dcts::static_for<N>([&](auto ir) DCTS_LAMBDA_INLINE { in[decltype(ir)::value] = v[decltype(ir)::value * N + c]; });
-    dcts::Dct2<N>::run(in, o);
-    o[0] *= dcts::kInvSqrt2;
-    dcts::static_for<N>([&](auto ir) DCTS_LAMBDA_INLINE { v[decltype(ir)::value * N + c] = o[decltype(ir)::value]; });
-  });
-  float e = 0.f;
-  dcts::static_for<N>([&](auto ir) DCTS_LAMBDA_INLINE {  // rows
-    constexpr int r = decltype(ir)::value;
-    float in[N], o[N];
-    dcts::static_for<N>([&](auto ic) DCTS_LAMBDA_INLINE { in[decltype(ic)::value] = v[r * N + decltype(ic)::value]; });
-    dcts::Dct2<N>::run(in, o);
-    o[0] *= dcts::kInvSqrt2;
-    dcts::static_for<N>([&](auto ic) DCTS_LAMBDA_INLINE { e = fmaf(o[decltype(ic)::value], o[decltype(ic)::value], e); });
-  });
-  constexpr float sc = float(4.0 / (double(N) * double(N)));
-  return e * sc;
-}
-
 __device__ __forceinline__ LaneGroup lane_group_of(const MapGeom& g, float* out, long long grp, int nn, int item) {
   LaneGroup gr;
   gr.m0 = grp * 64;
@@ -392,7 +372,9 @@ __global__ __launch_bounds__((64 * LaneCfg<N>::WAVES)) void k_energy_lane_multi(
 // VGPRs) as soon as pass 2 has read the transposed tile out of it, so the HBM latency of group
 // i+1 hides under the pass-2 codelet of group i instead of stalling the wave (s_waitcnt was
 // 28 % of the wave's cycles in k_energy_codelet). Pass 1 then reads its column from the linear
-// LDS image (lane = column: consecutive addresses, conflict-free).
+// LDS image (lane = column: consecutive addresses, conflict-free). The passes are those of
+// DCTS_CODELET_PASSES (codelet_schedule.hpp) with the prefetch issued between the pass-2 reads
+// and the pass-2 codelet, which is why they are written out here.
 template <int N>
 __global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_energy_codelet_dma(
     MapGeom g, float* __restrict__ out) {
@@ -489,10 +471,7 @@ __global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_energy_codelet_
 
 template <int HP, int WP, int PAD, bool STORE>
 int launch_codelet(const MapGeom& g, float* out, hipStream_t st) {
-  using Cfg = CodeletCfg<HP>;
-  const long long ngroups = (g.nmaps + Cfg::G - 1) / Cfg::G;
-  hipLaunchKernelGGL((k_energy_codelet<HP, WP, PAD, STORE>), dim3(codelet_grid<HP>(ngroups)), dim3(64 * Cfg::WAVES), 0, st, g, out);
-  return (int)hipGetLastError();
+  return launch_codelet_grid<HP>(k_energy_codelet<HP, WP, PAD, STORE>, g.nmaps, st, g, out);
 }
 
 template <int N>

@@ -1,7 +1,9 @@
-// codelet_schedule.hpp - what the kernels of the register-resident two-pass schedule (square tiles, edge <= 64) share:
-// the slab geometry and launch rules (CodeletCfg), the wavefront fence, the segmented reduction, and the host-side grid
-// rule, occupancy query and size switch. codelet.hip (fp32 energies and coefficients), band.hip (K weighted energies) and
-// half.hip (fp16 / bf16 inputs) hold the kernels.
+// codelet_schedule.hpp - the register-resident two-pass schedule (square tiles, edge <= 64), stated once: the slab geometry
+// and launch rules (CodeletCfg), and the plain form of the body - lane role, group walk, fp32 column load, both passes
+// through the wave's slab, energy epilogue - that band.hip, entropy.hip, half.hip and nhwc.hip build their kernels from;
+// each of them adds a load or an epilogue of its own. codelet.hip's kernels (the ones bench.py measures) keep their own
+// text of the body and say where they leave the plain form. Host side: the grid rule, the launch helper, the occupancy
+// query and the size switch.
 //
 // One wave owns G = floor(64 / N) maps per iteration. Pass 1: lane = column, the lane holds the whole column in VGPRs
 // (row r of a map is one contiguous segment across lanes: coalesced loads straight from HBM) and runs a straight-line
@@ -18,6 +20,7 @@
 #include "codelet_sizes.h"
 #include "dct_codelets.hpp"
 #include "dcts_internal.h"
+#include "grid_caps.h"
 
 namespace {
 
@@ -63,18 +66,136 @@ __device__ __forceinline__ void wave_fence() {
     }                                                           \
   }
 
-// ---- host side -------------------------------------------------------------------------------------------------------------
-// the grid rule: one wave per group, at most `cap` workgroups (the grid-stride loops take the rest), at least one
-inline unsigned grid_blocks(long long groups, int per_block, long long cap) {
-  long long blocks = (groups + per_block - 1) / per_block;
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (unsigned)blocks;
+// ---- the plain form of the body ----------------------------------------------------------------------------------------------
+// Four of the five pieces are macros, for the reason given at DCTS_MAP_SUM. As __forceinline__ functions (tried: the role as
+// a struct, load, passes and epilogue as templates) the same lines reach the kernel simplified in another order and every
+// kernel built from them compiles to other code: up to 48 more VGPRs, a wave per SIMD lost at some edges (DESIGN.md 4.2,
+// "The body, stated once"). As macros they compile to the code of the text they replace, instruction for instruction.
+// The macros declare what they produce (g1, c, act; xr; w; e) in the scope they are used in, in the order given here:
+//   DCTS_CODELET_LANE, [the group loop:] DCTS_CODELET_LOAD or a load of the kernel's own, DCTS_CODELET_PASSES,
+//   DCTS_CODELET_ENERGY or an epilogue of the kernel's own, wave_fence() before the slab is written again.
+
+// The lane's role for edge N: map g1 of the wave's group and column c in pass 1, row c of the same map in pass 2 (square
+// tile: one role for both). Lanes beyond G * N are idle (act == false).
+#define DCTS_CODELET_LANE(N, lane)                       \
+  const int g1 = (lane) / (N), c = (lane) - g1 * (N);    \
+  const bool act = g1 < CodeletCfg<N>::G;
+
+// The grid-stride walk over the groups of `nmaps` maps for a kernel of CodeletCfg<N>::WAVES one-group waves:
+//   for (grp = first; grp < ngroups; grp += step), the lane's map m1 = grp * G + g1, and it has one if act && m1 < nmaps.
+struct CodeletGroups {
+  long long first, step, ngroups;
+};
+template <int N>
+__device__ __forceinline__ CodeletGroups codelet_groups(long long nmaps) {
+  constexpr int G = CodeletCfg<N>::G, WAVES = CodeletCfg<N>::WAVES;
+  CodeletGroups w;
+  w.ngroups = (nmaps + G - 1) / G;
+  w.first = (long long)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  w.step = (long long)gridDim.x * WAVES;
+  return w;
 }
+
+// The fp32 column load: declares xr[N] = column c of map m1 of the MapGeom g (dense rows of N - PAD floats) behind PAD zero
+// rows and columns. PAD == 0 has no branch and no zero fill: lanes without a map (has == false) load some valid map
+// instead, and their results are never stored.
+#define DCTS_CODELET_LOAD(N, PAD, g, m1, c, has, xr)                                    \
+  float xr[N];                                                                          \
+  if constexpr (PAD == 0) {                                                             \
+    const float* p = map_base(g, (has) ? (m1) : (g).nmaps - 1) + ((has) ? (c) : 0);     \
+    dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {                                \
+      constexpr int r = decltype(i)::value;                                             \
+      xr[r] = p[r * (N - PAD)];                                                         \
+    });                                                                                 \
+  } else {                                                                              \
+    if ((has) && (c) >= PAD) {                                                          \
+      const float* p = map_base(g, m1) + ((c) - PAD);                                   \
+      dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {                              \
+        constexpr int r = decltype(i)::value;                                           \
+        if constexpr (r < PAD)                                                          \
+          xr[r] = 0.f;                                                                  \
+        else                                                                            \
+          xr[r] = p[(r - PAD) * (N - PAD)];                                             \
+      });                                                                               \
+    } else {                                                                            \
+      dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE { xr[decltype(i)::value] = 0.f; }); \
+    }                                                                                   \
+  }
+
+// Both passes: the lane's column xr[N] in; declares w[N], the N unnormalised coefficients of the lane's row. Through the
+// wave's slab `my` with plain transposing stores; idle lanes store nothing and read in bounds.
+#define DCTS_CODELET_PASSES(N, xr, w, my, g1, c, act)                                                             \
+  float dcts_y[N]; /* pass 1: column DCT-II, lane = column */                                                     \
+  dcts::Dct2<N>::run(xr, dcts_y);                                                                                 \
+  dcts_y[0] *= dcts::kInvSqrt2;                                                                                   \
+  if (act) {                                                                                                      \
+    float* dst = (my) + (g1) * CodeletCfg<N>::MAP_LDS + (c);                                                      \
+    dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {                                                          \
+      constexpr int kk = decltype(i)::value;                                                                      \
+      dst[kk * CodeletCfg<N>::S] = dcts_y[kk];                                                                    \
+    });                                                                                                           \
+  }                                                                                                               \
+  wave_fence();                                                                                                   \
+  float dcts_z[N], w[N]; /* pass 2: row DCT-II, lane = row */                                                     \
+  {                                                                                                               \
+    const float* src = (my) + ((act) ? (g1) : 0) * CodeletCfg<N>::MAP_LDS + ((act) ? (c) : 0) * CodeletCfg<N>::S; \
+    dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {                                                          \
+      constexpr int cc = decltype(i)::value;                                                                      \
+      dcts_z[cc] = src[cc];                                                                                       \
+    });                                                                                                           \
+  }                                                                                                               \
+  dcts::Dct2<N>::run(dcts_z, w);                                                                                  \
+  w[0] *= dcts::kInvSqrt2;
+
+// The energy epilogue: declares e, the row's squares summed in row order (0 in idle lanes), then over the map's lanes. The
+// map's lane c == 0 ends with the unscaled sum; times CodeletCfg<N>::SCALE it is the ortho energy.
+#define DCTS_CODELET_ENERGY(N, w, c, act, e)               \
+  float e = 0.f;                                           \
+  dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {     \
+    constexpr int l = decltype(i)::value;                  \
+    e = fmaf(w[l], w[l], e);                               \
+  });                                                      \
+  if (!(act)) e = 0.f;                                     \
+  DCTS_MAP_SUM(N, e, c)
+
+// The whole schedule in one lane, for kernels that give a lane a map of its own (no LDS, no cross-lane step): both passes
+// in registers, squares summed in (row, coefficient) order; returns the ortho energy.
+template <int N>
+__device__ __forceinline__ float lane_energy(float (&v)[N * N]) {
+  dcts::static_for<N>([&](auto ic) DCTS_LAMBDA_INLINE {  // columns, in place
+    constexpr int c = decltype(ic)::value;
+    float in[N], o[N];
+    dcts::static_for<N>([&](auto ir) DCTS_LAMBDA_INLINE { in[decltype(ir)::value] = v[decltype(ir)::value * N + c]; });
+    dcts::Dct2<N>::run(in, o);
+    o[0] *= dcts::kInvSqrt2;
+    dcts::static_for<N>([&](auto ir) DCTS_LAMBDA_INLINE { v[decltype(ir)::value * N + c] = o[decltype(ir)::value]; });
+  });
+  float e = 0.f;
+  dcts::static_for<N>([&](auto ir) DCTS_LAMBDA_INLINE {  // rows
+    constexpr int r = decltype(ir)::value;
+    float in[N], o[N];
+    dcts::static_for<N>([&](auto ic) DCTS_LAMBDA_INLINE { in[decltype(ic)::value] = v[r * N + decltype(ic)::value]; });
+    dcts::Dct2<N>::run(in, o);
+    o[0] *= dcts::kInvSqrt2;
+    dcts::static_for<N>([&](auto ic) DCTS_LAMBDA_INLINE { e = fmaf(o[decltype(ic)::value], o[decltype(ic)::value], e); });
+  });
+  constexpr float sc = float(4.0 / (double(N) * double(N)));
+  return e * sc;
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------
 template <int N>
 unsigned codelet_grid(long long groups) {
   using Cfg = CodeletCfg<N>;
-  return grid_blocks(groups, Cfg::WAVES, (long long)dctsi::num_cus() * Cfg::GRID_WAVES_PER_CU / Cfg::WAVES);
+  return dctsi::grid_blocks(groups, Cfg::WAVES, (long long)dctsi::num_cus() * Cfg::GRID_WAVES_PER_CU / Cfg::WAVES);
+}
+// launches `kernel` - workgroups of CodeletCfg<N>::WAVES waves, one group of G maps per wave and iteration - over nmaps maps
+template <int N, class... P, class... A>
+int launch_codelet_grid(void (*kernel)(P...), long long nmaps, hipStream_t st, const A&... args) {
+  using Cfg = CodeletCfg<N>;
+  const long long ngroups = (nmaps + Cfg::G - 1) / Cfg::G;
+  hipLaunchKernelGGL(kernel, dim3(codelet_grid<N>(ngroups)), dim3(64 * Cfg::WAVES), 0, st, args...);
+  return (int)hipGetLastError();
 }
 // workgroups of `kernel` (WAVES waves, static LDS only) that fit a CU, queried once: the persistent grids are one residency
 template <auto kernel, int WAVES>

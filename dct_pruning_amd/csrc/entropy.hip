@@ -4,9 +4,8 @@
 // and use the one-pass form:  e = sum w^2,  s = sum w^2 * ln(w^2) (a zero square adds 0),
 //   H = ln e - s / e, clamped into [+0.0, ln(H' * W')]; e == 0 (an all-zero map) gives +0.0.
 //
-//   k_entropy_codelet  the codelet kernel's schedule with the slab geometry, grid rule, fence and segmented reduction of
-//                      codelet_schedule.hpp: pass 1 lane = column, transpose through the wave's LDS slab, pass 2 lane =
-//                      row u with the N unnormalised coefficients of that row in registers. What this unit adds is the
+//   k_entropy_codelet  the two-pass schedule of codelet_schedule.hpp (its group loop, load and passes): a lane ends with
+//                      the N unnormalised coefficients of row u of its map in registers. What this unit adds is the
 //                      epilogue: two accumulators per lane (e, s) fed coefficient by coefficient in the row's order,
 //                      two segmented wave reductions, the final ln e - s / e in the map's lane 0, one store per map.
 //                      A lane's two chains and the reduction tree depend on nothing but the map's row: the result of
@@ -52,69 +51,18 @@ __device__ __forceinline__ float entropy_value(float e, float s, float hmax) {
 template <int N, int PAD>
 __global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_entropy_codelet(MapGeom g, float hmax, float* __restrict__ out) {
   using Cfg = CodeletCfg<N>;
-  constexpr int G = Cfg::G, S = Cfg::S, MAP_LDS = Cfg::MAP_LDS, WAVES = Cfg::WAVES;
-  constexpr int W = N - PAD;  // data row length == row stride (dense rows)
-  __shared__ float slab[WAVES][Cfg::WAVE_LDS];
-
+  __shared__ float slab[Cfg::WAVES][Cfg::WAVE_LDS];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   float* my = slab[wave];
-  const int g1 = lane / N, c = lane - g1 * N;  // square tile: (map, column) in pass 1, (map, row) in pass 2
-  const bool act = g1 < G;
+  DCTS_CODELET_LANE(N, lane)
 
-  const long long ngroups = (g.nmaps + G - 1) / G;
-  const long long wave_gid = (long long)blockIdx.x * WAVES + wave;
-  const long long nwaves = (long long)gridDim.x * WAVES;
-
-  for (long long grp = wave_gid; grp < ngroups; grp += nwaves) {
-    // ---- pass 1: column DCT-II, lane = column ---------------------------------------------------
-    const long long m1 = grp * G + g1;
+  const CodeletGroups walk = codelet_groups<N>(g.nmaps);
+  for (long long grp = walk.first; grp < walk.ngroups; grp += walk.step) {
+    const long long m1 = grp * Cfg::G + g1;
     const bool has = act && m1 < g.nmaps;
-    float xr[N];
-    if constexpr (PAD == 0) {
-      // lanes without a map load some valid map instead; their results are never stored
-      const float* p = map_base(g, has ? m1 : g.nmaps - 1) + (has ? c : 0);
-      dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-        constexpr int r = decltype(i)::value;
-        xr[r] = p[r * W];
-      });
-    } else {
-      if (has && c >= PAD) {
-        const float* p = map_base(g, m1) + (c - PAD);
-        dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-          constexpr int r = decltype(i)::value;
-          if constexpr (r < PAD)
-            xr[r] = 0.f;
-          else
-            xr[r] = p[(r - PAD) * W];
-        });
-      } else {
-        dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE { xr[decltype(i)::value] = 0.f; });
-      }
-    }
-    float y[N];
-    dcts::Dct2<N>::run(xr, y);
-    y[0] *= dcts::kInvSqrt2;
-    if (act) {
-      float* dst = my + g1 * MAP_LDS + c;
-      dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-        constexpr int kk = decltype(i)::value;
-        dst[kk * S] = y[kk];
-      });
-    }
-    wave_fence();
-
-    // ---- pass 2: row DCT-II, lane = row u ------------------------------------------------------
-    float z[N], w[N];
-    {
-      const float* src = my + (act ? g1 : 0) * MAP_LDS + (act ? c : 0) * S;
-      dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-        constexpr int cc = decltype(i)::value;
-        z[cc] = src[cc];
-      });
-    }
-    dcts::Dct2<N>::run(z, w);
-    w[0] *= dcts::kInvSqrt2;
+    DCTS_CODELET_LOAD(N, PAD, g, m1, c, has, xr)
+    DCTS_CODELET_PASSES(N, xr, w, my, g1, c, act)
     // ---- epilogue: the row's e and s, coefficient by coefficient in the row's order ----------------
     float e = 0.f, s = 0.f;
     dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE { entropy_term(w[decltype(i)::value], e, s); });
@@ -149,11 +97,8 @@ __global__ __launch_bounds__((64 * kReduceWaves)) void k_entropy_reduce(const fl
 
 template <int N, int PAD>
 int launch_entropy(const MapGeom& g, float* out, hipStream_t st) {
-  using Cfg = CodeletCfg<N>;
-  const long long ngroups = (g.nmaps + Cfg::G - 1) / Cfg::G;
   const float hmax = float(log(double(N) * double(N)));
-  hipLaunchKernelGGL((k_entropy_codelet<N, PAD>), dim3(codelet_grid<N>(ngroups)), dim3(64 * Cfg::WAVES), 0, st, g, hmax, out);
-  return (int)hipGetLastError();
+  return launch_codelet_grid<N>(k_entropy_codelet<N, PAD>, g.nmaps, st, g, hmax, out);
 }
 
 }  // namespace
@@ -167,10 +112,8 @@ int dispatch_entropy(int HP, int pad, const MapGeom& g, float* out, hipStream_t 
 }
 
 int launch_entropy_reduce(const float* coeff, long long nmaps, int hw, float* out, hipStream_t st) {
-  long long blocks = (nmaps + kReduceWaves - 1) / kReduceWaves;  // one wave per map
-  if (blocks > kReduceMaxBlocks) blocks = kReduceMaxBlocks;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_entropy_reduce, dim3((unsigned)blocks), dim3(64 * kReduceWaves), 0, st, coeff, nmaps, hw,
+  const unsigned blocks = grid_blocks(nmaps, kReduceWaves, kReduceMaxBlocks);  // one wave per map
+  hipLaunchKernelGGL(k_entropy_reduce, dim3(blocks), dim3(64 * kReduceWaves), 0, st, coeff, nmaps, hw,
                      float(log(double(hw))), out);
   return (int)hipGetLastError();
 }

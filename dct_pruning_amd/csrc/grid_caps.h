@@ -6,6 +6,15 @@
 
 namespace dctsi {
 
+// the grid rule of every grid-stride kernel: one unit of `per_block` per group, at most `cap` workgroups (the loops take
+// the rest), at least one
+inline unsigned grid_blocks(long long groups, int per_block, long long cap) {
+  long long blocks = (groups + per_block - 1) / per_block;
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  return (unsigned)blocks;
+}
+
 // rank.hip, k_rank: single-wave workgroups of 64 / G maps; grid-stride beyond (256 CUs x 32 workgroups)
 constexpr int kRankMaxBlocks = 8192;
 

@@ -1,8 +1,7 @@
 // half.hip - per-map DCT energy of IEEE fp16 and bfloat16 feature maps (dcts_energy_typed, include/dctscore.h).
 //
-//   k_energy_half    the fp32 codelet kernel's schedule with the slab geometry, grid rule, fence and segmented reduction of
-//                    codelet_schedule.hpp (plain transposing stores, the fp32 kernel's energy epilogue). What this unit adds
-//                    is the load: an element becomes fp32 EXACTLY (fp16 -> fp32 and bf16 -> fp32 are both exact, fp16
+//   k_energy_half    the two-pass schedule of codelet_schedule.hpp (its group loop, passes and energy epilogue). What this
+//                    unit adds is the load: an element becomes fp32 EXACTLY (fp16 -> fp32 and bf16 -> fp32 are both exact, fp16
 //                    subnormals included: they are fp32 normals) and every instruction after that is fp32 in the fp32
 //                    kernel's order. A map's value depends on that map alone: not on N, the channel slice, its position
 //                    in the wave or the launch count.
@@ -29,22 +28,15 @@ namespace {
 template <int N, int DT>
 __global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_energy_half(HalfGeom g, float* __restrict__ out) {
   using Cfg = CodeletCfg<N>;
-  constexpr int G = Cfg::G, S = Cfg::S, MAP_LDS = Cfg::MAP_LDS, WAVES = Cfg::WAVES;
-  __shared__ float slab[WAVES][Cfg::WAVE_LDS];
-
+  __shared__ float slab[Cfg::WAVES][Cfg::WAVE_LDS];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   float* my = slab[wave];
-  const int g1 = lane / N, c = lane - g1 * N;  // square tile: (map, column) in pass 1, (map, row) in pass 2
-  const bool act = g1 < G;
+  DCTS_CODELET_LANE(N, lane)
 
-  const long long ngroups = (g.nmaps + G - 1) / G;
-  const long long wave_gid = (long long)blockIdx.x * WAVES + wave;
-  const long long nwaves = (long long)gridDim.x * WAVES;
-
-  for (long long grp = wave_gid; grp < ngroups; grp += nwaves) {
-    // ---- pass 1: column DCT-II, lane = column ---------------------------------------------------
-    const long long m1 = grp * G + g1;
+  const CodeletGroups walk = codelet_groups<N>(g.nmaps);
+  for (long long grp = walk.first; grp < walk.ngroups; grp += walk.step) {
+    const long long m1 = grp * Cfg::G + g1;
     const bool has = act && m1 < g.nmaps;
     // lanes without a map load some valid map instead; their results are never stored
     const uint16_t* p = map_base(g, has ? m1 : g.nmaps - 1) + (has ? c : 0);
@@ -53,41 +45,9 @@ __global__ __launch_bounds__((64 * CodeletCfg<N>::WAVES)) void k_energy_half(Hal
       constexpr int r = decltype(i)::value;
       xr[r] = half_to_float<DT>(p[r * N]);
     });
-    float y[N];
-    dcts::Dct2<N>::run(xr, y);
-    y[0] *= dcts::kInvSqrt2;
-    if (act) {
-      float* dst = my + g1 * MAP_LDS + c;
-      dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-        constexpr int kk = decltype(i)::value;
-        dst[kk * S] = y[kk];
-      });
-    }
-    wave_fence();
-
-    // ---- pass 2: row DCT-II, lane = row u ------------------------------------------------------
-    float z[N], w[N];
-    {
-      const float* src = my + (act ? g1 : 0) * MAP_LDS + (act ? c : 0) * S;
-      dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-        constexpr int cc = decltype(i)::value;
-        z[cc] = src[cc];
-      });
-    }
-    dcts::Dct2<N>::run(z, w);
-    w[0] *= dcts::kInvSqrt2;
-    float e = 0.f;
-    dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-      constexpr int l = decltype(i)::value;
-      e = fmaf(w[l], w[l], e);
-    });
-    if (!act) e = 0.f;
-    // segmented reduction over the N lanes of each map (lane c == 0 ends with the sum)
-    DCTS_MAP_SUM(N, e, c)
-    if (has && c == 0) {
-      constexpr float sc = float(4.0 / (double(N) * double(N)));
-      out[m1] = e * sc;
-    }
+    DCTS_CODELET_PASSES(N, xr, w, my, g1, c, act)
+    DCTS_CODELET_ENERGY(N, w, c, act, e)
+    if (has && c == 0) out[m1] = e * Cfg::SCALE;
     wave_fence();
   }
 }
@@ -108,10 +68,7 @@ __global__ __launch_bounds__(kUpcastThreads) void k_upcast_half(HalfGeom g, int 
 
 template <int N, int DT>
 int launch_half(const HalfGeom& g, float* out, hipStream_t st) {
-  using Cfg = CodeletCfg<N>;
-  const long long ngroups = (g.nmaps + Cfg::G - 1) / Cfg::G;
-  hipLaunchKernelGGL((k_energy_half<N, DT>), dim3(codelet_grid<N>(ngroups)), dim3(64 * Cfg::WAVES), 0, st, g, out);
-  return (int)hipGetLastError();
+  return launch_codelet_grid<N>(k_energy_half<N, DT>, g.nmaps, st, g, out);
 }
 
 }  // namespace

@@ -5,15 +5,15 @@
 //
 //   k_nhwc_lane<N>    edges 2, 4, 7, 8. Lane = channel: the 64 lanes of a wave are 64 consecutive channels of one sample, a
 //                     lane holds its whole map in registers, so every load instruction is one contiguous run of 64 elements.
-//                     Both passes are Dct2<N>::run on register arrays: no LDS, no cross-lane step.
+//                     Both passes run in registers (lane_energy, codelet_schedule.hpp): no LDS, no cross-lane step.
 //   k_nhwc_block<N>   edges 14, 16, 28, 32. A workgroup takes one sample and CB consecutive channels, loads the [N*N][CB]
 //                     block with lanes along the channel axis first (each pixel one contiguous run of CB elements), and
 //                     writes it into LDS as CB maps. After one barrier each wave owns G = 64 / N of those maps and runs the
-//                     codelet schedule of codelet_schedule.hpp on them, xr[r] read from LDS; its transpose slab overlays
-//                     the maps it has just read.
+//                     passes and the energy epilogue of codelet_schedule.hpp on them, xr[r] read from LDS; its transpose
+//                     slab overlays the maps it has just read.
 //   k_nhwc_strip      edge 56. One sample and 4 channels per workgroup, one wave per map; the block goes through LDS in
-//                     strips of 8 rows from which each wave picks its map's column values, then the two passes through
-//                     the wave's own transpose slab.
+//                     strips of 8 rows from which each wave picks its map's column values, then the same passes and
+//                     epilogue through the wave's own transpose slab.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -67,27 +67,8 @@ __global__ __launch_bounds__(64 * kLaneWaves) void k_nhwc_lane(NhwcGeom g, float
       constexpr int h = decltype(i)::value / N, w = decltype(i)::value % N;
       v[h * N + w] = load_elem<DT>(p + (long long)h * g.strideH + (long long)w * g.strideW);
     });
-    // ---- pass 1: column DCT-II of every column ------------------------------------------------------
-    float t[N * N];
-    dcts::static_for<N>([&](auto iw) DCTS_LAMBDA_INLINE {
-      constexpr int w = decltype(iw)::value;
-      float col[N], y[N];
-      dcts::static_for<N>([&](auto ir) DCTS_LAMBDA_INLINE { col[decltype(ir)::value] = v[decltype(ir)::value * N + w]; });
-      dcts::Dct2<N>::run(col, y);
-      y[0] *= dcts::kInvSqrt2;
-      dcts::static_for<N>([&](auto ik) DCTS_LAMBDA_INLINE { t[decltype(ik)::value * N + w] = y[decltype(ik)::value]; });
-    });
-    // ---- pass 2: row DCT-II of every row u, squares summed in (u, l) order ---------------------------
-    float e = 0.f;
-    dcts::static_for<N>([&](auto iu) DCTS_LAMBDA_INLINE {
-      constexpr int u = decltype(iu)::value;
-      float z[N], wv[N];
-      dcts::static_for<N>([&](auto ic) DCTS_LAMBDA_INLINE { z[decltype(ic)::value] = t[u * N + decltype(ic)::value]; });
-      dcts::Dct2<N>::run(z, wv);
-      wv[0] *= dcts::kInvSqrt2;
-      dcts::static_for<N>([&](auto il) DCTS_LAMBDA_INLINE { e = fmaf(wv[decltype(il)::value], wv[decltype(il)::value], e); });
-    });
-    if (has) out[n * g.c_count + j] = e * CodeletCfg<N>::SCALE;
+    const float e = lane_energy<N>(v);
+    if (has) out[n * g.c_count + j] = e;
   }
 }
 
@@ -118,14 +99,13 @@ __global__ __launch_bounds__((NhwcBlockCfg<N>::THREADS)) void k_nhwc_block(NhwcG
   using T = typename NhwcElem<DT>::type;
   using B = NhwcBlockCfg<N>;
   using Cfg = CodeletCfg<N>;
-  constexpr int G = Cfg::G, S = Cfg::S, MAP_LDS = Cfg::MAP_LDS, CB = B::CB, MS = B::MS;
+  constexpr int G = Cfg::G, CB = B::CB, MS = B::MS;
   __shared__ float blk[CB * MS];
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int ch = threadIdx.x % CB, p0 = threadIdx.x / CB;  // staging role: lanes run along the channel axis first
-  const int g1 = lane / N, c = lane - g1 * N;              // codelet role: (map, column) in pass 1, (map, row) in pass 2
-  const bool act = g1 < G;
+  DCTS_CODELET_LANE(N, lane)                               // codelet role: (map, column) in pass 1, (map, row) in pass 2
   float* my = blk + wave * G * MS;                         // the wave's G maps, then its transpose slab
 
   const long long cblocks = (g.c_count + CB - 1) / CB;     // channel blocks per sample: the fastest-varying index
@@ -161,7 +141,7 @@ __global__ __launch_bounds__((NhwcBlockCfg<N>::THREADS)) void k_nhwc_block(NhwcG
     }
     __syncthreads();
 
-    // ---- pass 1: column DCT-II, lane = column, xr[r] from the wave's own maps in LDS ------------------------------
+    // ---- the wave's own maps: xr[r] from LDS, lane = column, then the shared passes and epilogue ----------------------
     const int jm = c0 + wave * G + g1;
     const bool has = act && jm < g.c_count;
     float xr[N];
@@ -173,37 +153,8 @@ __global__ __launch_bounds__((NhwcBlockCfg<N>::THREADS)) void k_nhwc_block(NhwcG
       });
     }
     wave_fence();  // the slab overlays the maps just read
-    float y[N];
-    dcts::Dct2<N>::run(xr, y);
-    y[0] *= dcts::kInvSqrt2;
-    if (act) {
-      float* dst = my + g1 * MAP_LDS + c;
-      dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-        constexpr int kk = decltype(i)::value;
-        dst[kk * S] = y[kk];
-      });
-    }
-    wave_fence();
-
-    // ---- pass 2: row DCT-II, lane = row u ------------------------------------------------------
-    float z[N], w[N];
-    {
-      const float* src = my + (act ? g1 : 0) * MAP_LDS + (act ? c : 0) * S;
-      dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-        constexpr int cc = decltype(i)::value;
-        z[cc] = src[cc];
-      });
-    }
-    dcts::Dct2<N>::run(z, w);
-    w[0] *= dcts::kInvSqrt2;
-    float e = 0.f;
-    dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-      constexpr int l = decltype(i)::value;
-      e = fmaf(w[l], w[l], e);
-    });
-    if (!act) e = 0.f;
-    // segmented reduction over the N lanes of each map (lane c == 0 ends with the sum)
-    DCTS_MAP_SUM(N, e, c)
+    DCTS_CODELET_PASSES(N, xr, w, my, g1, c, act)
+    DCTS_CODELET_ENERGY(N, w, c, act, e)
     if (has && c == 0) out[n * g.c_count + jm] = e * Cfg::SCALE;
     __syncthreads();  // the next item's staging overwrites every wave's maps
   }
@@ -230,7 +181,7 @@ __global__ __launch_bounds__(NhwcStripCfg::THREADS) void k_nhwc_strip(NhwcGeom g
   using B = NhwcStripCfg;
   constexpr int N = B::N;
   using Cfg = CodeletCfg<N>;
-  constexpr int S = Cfg::S, CB = B::CB, R = B::R, CS = B::CS;
+  constexpr int CB = B::CB, R = B::R, CS = B::CS;
   static_assert(Cfg::G == 1, "one map per wave");
   __shared__ float slab[B::WAVES][Cfg::WAVE_LDS];
   __shared__ float strip[CB * CS];
@@ -238,7 +189,8 @@ __global__ __launch_bounds__(NhwcStripCfg::THREADS) void k_nhwc_strip(NhwcGeom g
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int ch = threadIdx.x % CB, p0 = threadIdx.x / CB;  // staging role: lanes run along the channel axis first
-  const int c = lane;                                      // codelet role: column in pass 1, row in pass 2
+  constexpr int g1 = 0;                                    // codelet role, one map per wave: column in pass 1, row in pass 2
+  const int c = lane;
   const bool act = lane < N;
 
   const long long cblocks = (g.c_count + CB - 1) / CB;     // channel blocks per sample: the fastest-varying index
@@ -276,40 +228,10 @@ __global__ __launch_bounds__(NhwcStripCfg::THREADS) void k_nhwc_strip(NhwcGeom g
 
     const int jm = c0 + wave;
     const bool has = jm < g.c_count;
-    {
-        float* my = slab[wave];
-        // ---- pass 1: column DCT-II, lane = column ---------------------------------------------------
-        float y[N];
-        dcts::Dct2<N>::run(xr, y);
-        y[0] *= dcts::kInvSqrt2;
-        if (act) {
-          float* dst = my + c;
-          dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-            constexpr int kk = decltype(i)::value;
-            dst[kk * S] = y[kk];
-          });
-        }
-        wave_fence();
-        // ---- pass 2: row DCT-II, lane = row u ------------------------------------------------------
-        float z[N], w[N];
-        {
-          const float* src = my + (act ? c : 0) * S;
-          dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-            constexpr int cc = decltype(i)::value;
-            z[cc] = src[cc];
-          });
-        }
-        dcts::Dct2<N>::run(z, w);
-        w[0] *= dcts::kInvSqrt2;
-        float e = 0.f;
-        dcts::static_for<N>([&](auto i) DCTS_LAMBDA_INLINE {
-          constexpr int l = decltype(i)::value;
-          e = fmaf(w[l], w[l], e);
-        });
-        if (!act) e = 0.f;
-        DCTS_MAP_SUM(N, e, c)
-        if (has && c == 0) out[n * g.c_count + jm] = e * Cfg::SCALE;
-    }
+    float* my = slab[wave];
+    DCTS_CODELET_PASSES(N, xr, w, my, g1, c, act)
+    DCTS_CODELET_ENERGY(N, w, c, act, e)
+    if (has && c == 0) out[n * g.c_count + jm] = e * Cfg::SCALE;
     __syncthreads();  // the next item's strips follow
   }
 }

@@ -152,9 +152,8 @@ int launch_running_mean_multi(const dcts_update_desc* descs, int n, long long cm
 }
 
 int launch_weighted_reduce(const float* coeff, const float* weights, long long nmaps, int hw, float* out, hipStream_t st) {
-  long long blocks = (nmaps + kReduceWaves - 1) / kReduceWaves;  // one wave per map
-  if (blocks > kReduceMaxBlocks) blocks = kReduceMaxBlocks;
-  hipLaunchKernelGGL(k_weighted_energy, dim3((unsigned)blocks), dim3(64 * kReduceWaves), 0, st, coeff, weights, nmaps, hw, out);
+  const unsigned blocks = grid_blocks(nmaps, kReduceWaves, kReduceMaxBlocks);  // one wave per map
+  hipLaunchKernelGGL(k_weighted_energy, dim3(blocks), dim3(64 * kReduceWaves), 0, st, coeff, weights, nmaps, hw, out);
   return (int)hipGetLastError();
 }
 
