@@ -11,7 +11,8 @@ and a fourth, the spectral entropy of the DCT coefficients (spectral_entropy_nc,
 number per map that does depend on the transform. A fifth looks at more than one map at a time: the summed distance of
 every map to the other maps of its layer (gm_distance_nc, imp_score(criterion="gm")), FPGM's geometric-median rule on feature maps;
 its terms, the [C, C] matrix of pair distances per layer (gm_pair_matrix, imp_score(criterion="gm", gm_pairs=True)), feed the
-host-side selection rules of pairs.py (row sum, nearest neighbour, farthest point).
+host-side selection rules of pairs.py (row sum, nearest neighbour, farthest point). With lowpass=K both compare the maps' K x K
+lowest DCT coefficients (lowpass_nc, imp_score(criterion="gm", gm_lowpass=K)): the one form of that distance the transform changes.
 """
 from .ops import (  # noqa: F401
     ALGO_AUTO,
@@ -37,9 +38,10 @@ from .ops import (  # noqa: F401
     has_entropy_kernel,
     has_half_kernel,
     has_nhwc_kernel,
+    lowpass_nc,
     rank_nc,
     spectral_entropy_nc,
     weighted_energy_nc,
 )
 
-__all__ = ["energy_nc", "energy_multi", "energy_mixed", "dct2d", "batch_sum", "has_codelet", "weighted_energy_nc", "rank_nc", "band_energy_nc", "has_band_kernel", "has_half_kernel", "has_nhwc_kernel", "spectral_entropy_nc", "has_entropy_kernel", "gm_distance_nc", "gm_pair_matrix", "ALGO_AUTO", "ALGO_DIRECT", "ALGO_CODELET", "ALGO_SPLIT", "ALGO_PREFETCH", "ALGO_FUSED", "ALGO_PIPE", "ALGO_LANE", "ALGO_TILE2D", "ALGO_RECT"]
+__all__ = ["energy_nc", "energy_multi", "energy_mixed", "dct2d", "batch_sum", "has_codelet", "weighted_energy_nc", "rank_nc", "band_energy_nc", "has_band_kernel", "has_half_kernel", "has_nhwc_kernel", "spectral_entropy_nc", "has_entropy_kernel", "gm_distance_nc", "gm_pair_matrix", "lowpass_nc", "ALGO_AUTO", "ALGO_DIRECT", "ALGO_CODELET", "ALGO_SPLIT", "ALGO_PREFETCH", "ALGO_FUSED", "ALGO_PIPE", "ALGO_LANE", "ALGO_TILE2D", "ALGO_RECT"]

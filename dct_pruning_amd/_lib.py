@@ -57,6 +57,9 @@ SIGNATURES = {
     "dcts_gm_pairs_slices": (_i32, [_i64, _i32]),
     "dcts_gm_pairs_f32": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp,
                                          _i32, _vp, _sz]),
+    "dcts_dct2d_lowpass_workspace_bytes": (_sz, [_i64, _i32, _i64, _i64, _i32]),
+    "dcts_dct2d_lowpass_f32": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
+                                              _vp, _vp, _sz, _vp]),
     "dcts_energy_typed": (ctypes.c_int, [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                          _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     "dcts_typed_workspace_bytes": (_sz, [_i32, _i64, _i64, _i64, _i64]),

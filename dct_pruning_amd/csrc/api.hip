@@ -8,7 +8,7 @@
 // 2-D DCT-II and the squared coefficients are reduced to one fp32 energy per map.
 //
 // The kernel families are units of their own (codelet.hip, split.hip, fused.hip, fused2.hip, pipe.hip, tile2d.hip,
-// tile2g.hip, rect.hip, rank.hip, band.hip, entropy.hip, gm.hip, gm_pairs.hip, half.hip, nhwc.hip, direct.hip: the cosine-matrix fallback for any
+// tile2g.hip, rect.hip, rank.hip, band.hip, entropy.hip, lowpass.hip, gm.hip, gm_pairs.hip, half.hip, nhwc.hip, direct.hip: the cosine-matrix fallback for any
 // (H, W) <= DCTS_MAX_EDGE, reduce.hip: batch sum, running mean, weighted reduction). What stays here of the direct family is
 // the memo of its basis tables: which workspace holds which tables is host policy.
 #include <hip/hip_runtime.h>
@@ -416,11 +416,13 @@ size_t coeff_layout_bytes(int64_t nmaps, int HP, int WP) {
   return coeff_fixed(HP, WP) + 2 * (size_t)(chunk * tile);
 }
 // Whole samples per chunk where the chunk holds one and one strided view can cover them, else runs of channels of one sample.
+// `algo`: the coefficient path of the inner calls; kCoeffAlgoOwn: what coeff_algo() names for the tensor.
+constexpr int kCoeffAlgoOwn = -1;
 template <class Reduce>
-int coeff_fallback(const TensorView& v, void* workspace, size_t workspace_bytes, void* stream, Reduce reduce) {
+int coeff_fallback(const TensorView& v, void* workspace, size_t workspace_bytes, void* stream, Reduce reduce, int algo = kCoeffAlgoOwn) {
   const CoeffWs w = coeff_layout(workspace, workspace_bytes, (int)v.HP(), (int)v.WP());
   if (w.chunk < 1) return DCTS_E_WORKSPACE;
-  const int algo = coeff_algo(v);
+  if (algo == kCoeffAlgoOwn) algo = coeff_algo(v);
   const bool whole_samples = w.chunk >= v.c_count && (v.contiguous() || algo == DCTS_ALGO_AUTO);
   return coeff_chunks(v, w, whole_samples, algo, workspace, workspace_bytes, stream, reduce);
 }
@@ -610,6 +612,41 @@ int dcts_spectral_entropy_f32(const float* x, int64_t N, int64_t C_total, int64_
   return coeff_fallback(v, workspace, workspace_bytes, stream, [&](int64_t nmaps, int64_t first) {
     return launch_entropy_reduce(reinterpret_cast<float*>(workspace), nmaps, HP * WP, out_nc + first, st);
   });
+}
+
+// ---- the low-pass DCT signature of every map (lowpass.hip) -------------------------------------------------------------
+// The fused kernel needs no workspace; the fallback is the band / entropy fallback with a gather in place of the reduction. Its
+// inner calls ask for DCTS_ALGO_AUTO, the path dcts_dct2d_f32 takes: the signature is the corner of that call's output bit for
+// bit, whatever the chunking.
+namespace {
+bool lowpass_fused(int64_t H, int64_t W) { return has_codelet(H, W); }
+}  // namespace
+
+size_t dcts_dct2d_lowpass_workspace_bytes(int64_t N, int32_t c_count, int64_t H, int64_t W, int32_t K) {
+  if (N <= 0 || c_count <= 0 || H <= 0 || W <= 0 || K < 1) return 0;
+  if (H > DCTS_MAX_EDGE || W > DCTS_MAX_EDGE) return 0;
+  if (lowpass_fused(H, W)) return 0;
+  return align_up(coeff_layout_bytes(N * (int64_t)c_count, (int)H, (int)W), 256);
+}
+
+int dcts_dct2d_lowpass_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W, int64_t strideN, int64_t strideC,
+                           int64_t strideH, int64_t strideW, int32_t c_begin, int32_t c_count, int32_t K, int32_t flags,
+                           float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  const TensorView v = view_of(x, N, C_total, H, W, strideN, strideC, strideH, strideW, c_begin, c_count, /*pad_front_if_odd=*/0);
+  if (const int rc = validate(v, {out}, Checks::All)) return rc;
+  if (K < 1) return DCTS_E_SHAPE;
+  if (flags & ~DCTS_LOWPASS_DROP_DC) return DCTS_E_UNSUPPORTED;
+  const int drop_dc = (flags & DCTS_LOWPASS_DROP_DC) ? 1 : 0;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const MapGeom g = map_geom(v);
+  if (lowpass_fused(H, W) && v.dense_square()) return dispatch_lowpass((int)H, g, K, drop_dc, out, st);
+  // fallback: one gather per chunk that copies the corner of every tile
+  if (!workspace) return DCTS_E_WORKSPACE;
+  if (reinterpret_cast<uintptr_t>(workspace) & 15) return DCTS_E_ALIGN;
+  const int Kh = (int)(K < H ? K : H), Kw = (int)(K < W ? K : W);
+  return coeff_fallback(v, workspace, workspace_bytes, stream, [&](int64_t nmaps, int64_t first) {
+    return launch_lowpass_gather(reinterpret_cast<float*>(workspace), nmaps, first, g, Kh, Kw, drop_dc, out, st);
+  }, DCTS_ALGO_AUTO);
 }
 
 // ---- the summed distance of every scored map to a reference set (gm.hip) ------------------------------------------------

@@ -196,6 +196,15 @@ int dispatch_entropy(int HP, int pad, const MapGeom& g, float* out, hipStream_t 
 // fallback reduction: out[m] = entropy of the squares of `nmaps` dense tiles of `hw` coefficients (any common scale)
 int launch_entropy_reduce(const float* coeff, long long nmaps, int hw, float* out, hipStream_t st);
 
+// ---- lowpass.hip: the K x K lowest DCT coefficients of every map (dcts_dct2d_lowpass_f32) -----------------------------
+// fused kernel for dense square unpadded tiles with a codelet: one launch, no workspace; out is [nmaps][k][k], k = min(K, HP).
+// drop_dc: [0][0] is written as +0.0 and a map whose elements are all equal gets an all-+0.0 signature.
+int dispatch_lowpass(int HP, const MapGeom& g, int K, int drop_dc, float* out, hipStream_t st);
+// fallback "reduction": the [Kh][Kw] corner of `nmaps` dense [g.H][g.W] tiles of coefficients to out[first + m]; g is the call's
+// whole view, whose map first + m is the spatial map of tile m (read for the flat rule of drop_dc only)
+int launch_lowpass_gather(const float* coeff, long long nmaps, long long first, const MapGeom& g, int Kh, int Kw, int drop_dc,
+                          float* out, hipStream_t st);
+
 // ---- gm.hip: summed distance of every scored map to the maps of a reference set (dcts_gm_distance_f32) -----------------
 // Dense maps of hw = H * W elements; the scored channels [c_begin, c_begin + c_count) and the reference channels
 // [r_begin, r_begin + r_count) of every sample. One launch, no workspace.

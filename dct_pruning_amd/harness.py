@@ -54,7 +54,15 @@ Additions (opt-in, results identical on fixed batches):
                       dct_pruning_amd.pairs turns it into imp_*.npy under a selection rule (row sum, nearest neighbour,
                       farthest point) afterwards, on the host, as bands.collapse does for a spectrum. Its value is the fp32
                       sum of the batch matrices in batch order divided once by the number of samples
-                      (accumulate.PairAccumulator), in every schedule and for every world size;
+                      (accumulate.PairAccumulator), in every schedule and for every world size. gm_lowpass=K > 0 compares the
+                      maps' low-pass signatures, their K x K lowest DCT coefficients (dcts_dct2d_lowpass_f32,
+                      ops.gm_distance_nc(lowpass=K) / ops.gm_pair_matrix(lowpass=K)), instead of the maps: the one form of
+                      the distance that depends on the transform, under which maps that share their coarse structure and
+                      differ in texture or noise are close. It combines with gm_metric and gm_pairs and every schedule.
+                      Square maps of an edge with a codelet (every hook point of the six classification nets) take one
+                      fused pass and the score is several times faster than plain gm; u2netp's hook shapes (72 ... 288)
+                      take dct2d's coefficient path and are slower than plain gm (DESIGN.md 7k);
+                      the output dir is gm_score/<net>_limit<L>[_<metric>]_low<K>[_pairs]/;
   autocast="fp16" | "bf16"
                       the forward sweeps run under torch.autocast; the hooks hand the tensors to ops.energy_nc in
                       whatever dtype arrives (float16 / bfloat16 maps are scored natively, dcts_energy_typed; a tensor
@@ -96,6 +104,8 @@ _band_cfg = (4, "square")
 _band_weight_cache = {}
 # the gm criterion's metric: imp_score(criterion="gm", gm_metric=...) sets it for its hooks, on every call
 _gm_metric = "l2"
+# the gm criterion's low-pass band (0: the maps as they are): imp_score(criterion="gm", gm_lowpass=...) sets it likewise
+_gm_lowpass = 0
 
 
 def _band_weights(H, W, device):
@@ -128,18 +138,27 @@ def _score_entropy(x, c_begin, c_count, pad):
     return _entropy_nc(x, c_begin=c_begin, c_count=c_count, pad_front_if_odd=pad)
 
 
+def _gm_kwargs():
+    """The metric and the low-pass band, each named only where it is not the default's: "l2" on whole maps is the call it
+    always was."""
+    kw = {} if _gm_metric == "l2" else {"metric": _gm_metric}
+    if _gm_lowpass:
+        kw["lowpass"] = _gm_lowpass
+    return kw
+
+
 def _score_gm(x, c_begin, c_count, pad, ref):
     """The summed distance to the maps of `ref` = (begin, count), the hook kind's whole channel set, whichever channel range
-    of it is scored here (no odd pad: zeros in front of both maps change no distance). The metric is named only where it is
-    not the default's: "l2" is the call it always was."""
-    kw = {} if _gm_metric == "l2" else {"metric": _gm_metric}
+    of it is scored here (no odd pad: zeros in front of both maps change no distance). The metric and the low-pass band are
+    named only where they are not the default's (_gm_kwargs)."""
+    kw = _gm_kwargs()
     return _gm_nc(x, c_begin=c_begin, c_count=c_count, ref_begin=ref[0], ref_count=ref[1], **kw)
 
 
 def _pair_matrix(x, c_begin, c_count, ref):
     """gm's option gm_pairs: the [c_count, ref[1]] distances of a channel range to the maps of `ref`, summed over the samples
-    of x. The metric is named as _score_gm names it."""
-    kw = {} if _gm_metric == "l2" else {"metric": _gm_metric}
+    of x. The metric and the low-pass band are named as _score_gm names them."""
+    kw = _gm_kwargs()
     return _gm_pairs_nc(x, c_begin=c_begin, c_count=c_count, ref_begin=ref[0], ref_count=ref[1], **kw)
 
 
@@ -438,7 +457,7 @@ class _ChannelsLastLoader:
 
 
 def check_options(criterion, net, deferred=False, autocast=None, channels_last=False, bands=(4, "square"), gm_metric="l2",
-                  gm_pairs=False):
+                  gm_pairs=False, gm_lowpass=0):
     """Raises the ValueError of the first rule an imp_score call with these options breaks: what the criterion's row
     supports, and the two rules that hold for every criterion (autocast and channels_last have no deferred mode,
     channels_last does not cover u2netp). importance_generation.py's parser rejects its command lines with it."""
@@ -452,6 +471,14 @@ def check_options(criterion, net, deferred=False, autocast=None, channels_last=F
                          % (gm_metric, criterion))
     if gm_pairs and not crit.cross:
         raise ValueError("imp_score: gm_pairs goes with criterion='gm' only (the %s criterion compares no maps)" % criterion)
+    if isinstance(gm_lowpass, bool) or not isinstance(gm_lowpass, (int, np.integer)) or gm_lowpass < 0:
+        raise ValueError("imp_score: gm_lowpass must be an integer >= 0 (0: whole maps), got %r" % (gm_lowpass,))
+    if gm_lowpass:
+        if not crit.cross:
+            raise ValueError("imp_score: gm_lowpass goes with criterion='gm' only (the %s criterion compares no maps)" % criterion)
+        if gm_lowpass == 1 and gm_metric == "correlation":
+            raise ValueError("imp_score: gm_lowpass=1 keeps the DC coefficient alone, which gm_metric='correlation' removes: "
+                             "nothing is left to compare")
     if autocast is not None:
         if autocast not in AUTOCAST:
             raise ValueError("imp_score: autocast must be None, 'fp16' or 'bf16', got %r" % (autocast,))
@@ -480,7 +507,8 @@ def check_options(criterion, net, deferred=False, autocast=None, channels_last=F
 
 
 def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host", group=None, deferred=False,
-              criterion="dct", bands=(4, "square"), autocast=None, channels_last=False, gm_metric="l2", gm_pairs=False):
+              criterion="dct", bands=(4, "square"), autocast=None, channels_last=False, gm_metric="l2", gm_pairs=False,
+              gm_lowpass=0):
     """Counterpart of utils/common.py:367-977. `args` needs .net, .limit (and whatever
     load_data reads when train_loader is None). criterion="rank" scores HRank's feature-map rank instead of the
     DCT energy and writes rank_conv/<net>_limit<L>/rank_*.npy. criterion="bands" with bands=(K, kind) writes the
@@ -491,13 +519,16 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
     gm_metric="cosine" / "correlation" the distance is taken between unit maps and the files go to
     gm_score/<net>_limit<L>_<metric>/ (criterion "gm" only). gm_pairs=True (criterion "gm" only) writes the [c, c] matrix of
     mean pair distances per file instead, to gm_score/<net>_limit<L>[_<metric>]_pairs/, for dct_pruning_amd.pairs to score.
+    gm_lowpass=K > 0 (criterion "gm" only; not K = 1 with "correlation") takes every distance between the maps' K x K lowest
+    DCT coefficients instead of the maps; those files go to gm_score/<net>_limit<L>[_<metric>]_low<K>[_pairs]/.
     autocast="fp16" / "bf16" runs the forward sweeps under torch.autocast and scores the half-precision tensors the
     hooks then see as they are (criterion "dct" only, not with deferred).
     channels_last=True converts the net (in place) and every input batch to torch.channels_last; the tensors the hooks
     then see are scored in the layout they arrive in (criterion "dct" only, not with deferred, not u2netp)."""
-    global _acc, _band_cfg, _gm_metric
-    check_options(criterion, args.net, deferred, autocast, channels_last, bands, gm_metric, gm_pairs)
+    global _acc, _band_cfg, _gm_metric, _gm_lowpass
+    check_options(criterion, args.net, deferred, autocast, channels_last, bands, gm_metric, gm_pairs, gm_lowpass)
     _gm_metric = gm_metric
+    _gm_lowpass = int(gm_lowpass)
     crit = _TABLE[criterion]
     if not hasattr(args, "limit"):
         # utils/load_models.py:819 calls imp_score from prune_*.py whose parsers define no --limit
@@ -512,6 +543,8 @@ def imp_score(net, args, train_loader=None, single_sweep=False, accumulate="host
         out_dir += "_%s%d" % (_band_cfg[1], width)
     if gm_metric != "l2":
         out_dir += "_" + gm_metric
+    if gm_lowpass:
+        out_dir += "_low%d" % gm_lowpass
     if gm_pairs:
         out_dir += "_pairs"
     world, rank = 1, 0

@@ -350,10 +350,68 @@ def rank_nc(x, c_begin=0, c_count=None, out=None):
     return out
 
 
+LOWPASS_DROP_DC = 1  # DCTS_LOWPASS_DROP_DC
+
+
+def lowpass_nc(x, K, c_begin=0, c_count=None, drop_dc=False, out=None):
+    """S[n, j] = dct_2d(x[n, c_begin+j], norm='ortho')[:K, :K] -> [N, c_count, min(K, H), min(K, W)] fp32.
+
+    The low-pass signature of every map (dcts_dct2d_lowpass_f32): its K x K lowest DCT coefficients and nothing else, in one
+    pass that reads the map once. An edge shorter than K keeps all its coefficients. drop_dc=True writes S[..., 0, 0] as +0.0
+    (the signature of the centred map) and gives a flat map - every element equal, all-zero maps included - an all-+0.0
+    signature; the test is made on the map itself, exactly. Dense square maps of an edge has_codelet names take one fused
+    launch; every other shape up to 512 and every tensor whose rows have a pitch take the coefficient path of dct2d into the
+    workspace and a gather, and give the corner of dct2d's output bit for bit.
+    float32 NCHW only; a tensor whose rows are not W-contiguous is copied with .contiguous() first. `out`: a contiguous
+    float32 tensor of the result's shape on x's device to overwrite. Enqueues on the current stream of x's device; no
+    synchronisation."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("lowpass_nc needs K >= 1, got %r" % (K,))
+    x, c_begin, c_count, _, stream = _open(x, c_begin, c_count, out=False)
+    N, C, H, W = x.shape
+    shape = (N, c_count, min(K, H), min(K, W))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif out.shape != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous float32 %s tensor on x's device" % (list(shape),))
+    lib = _lib.load()
+    nbytes = lib.dcts_dct2d_lowpass_workspace_bytes(N, c_count, H, W, K)
+    if nbytes == 0 and (x.stride(2) != W or x.stride(1) != H * W):
+        # a fused shape that takes the fallback: sized as the header says, for (H, W + 1)
+        nbytes = lib.dcts_dct2d_lowpass_workspace_bytes(N, c_count, H, W + 1, K)
+    ws = _workspace(x.device, stream, nbytes) if nbytes else None
+    _launch(x.device, lib.dcts_dct2d_lowpass_f32,
+            x.data_ptr(), N, C, H, W, x.stride(0), x.stride(1), x.stride(2), x.stride(3), c_begin, c_count, K,
+            LOWPASS_DROP_DC if drop_dc else 0, out.data_ptr(), ws.data_ptr() if nbytes else None, ws.numel() if nbytes else 0,
+            stream)
+    return out
+
+
 GM_METRICS = {"l2": 0, "cosine": 1, "correlation": 2}  # DCTS_GM_*
 
 
-def gm_distance_nc(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, out=None, metric="l2"):
+def _gm_lowpass(fn, x, K, c_begin, c_count, ref_begin, ref_count, metric, out):
+    """fn (gm_distance_nc or gm_pair_matrix) on the low-pass signatures of x: those of the channel hull of the two ranges,
+    with both ranges shifted by the hull's start. "correlation" drops the DC term, which is the centring, and then compares
+    as "cosine" does."""
+    K = int(K)
+    if K < 0:
+        raise ValueError("lowpass must be >= 0, got %r" % (K,))
+    if metric not in GM_METRICS:
+        raise ValueError("metric must be one of %s, got %r" % (", ".join(GM_METRICS), metric))
+    if K == 1 and metric == "correlation":
+        raise ValueError("lowpass=1 under metric='correlation' keeps the DC term alone, which the centring removes: nothing is left")
+    _check_input(x)
+    c_begin, c_count = _slice(x, c_begin, c_count)
+    ref_begin, ref_count = _slice(x, ref_begin, ref_count)
+    lo, hi = min(c_begin, ref_begin), max(c_begin + c_count, ref_begin + ref_count)
+    sig = lowpass_nc(x, K, c_begin=lo, c_count=hi - lo, drop_dc=(metric == "correlation"))
+    return fn(sig, c_begin=c_begin - lo, c_count=c_count, ref_begin=ref_begin - lo, ref_count=ref_count, out=out,
+              metric="cosine" if metric == "correlation" else metric)
+
+
+def gm_distance_nc(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, out=None, metric="l2", lowpass=0):
     """G[n, j] = sum_k ||x[n, c_begin+j] - x[n, k]||_2 over the reference channels k in [ref_begin, ref_begin + ref_count)
     -> [N, c_count] fp32 (ref_count None = to the end).
 
@@ -366,8 +424,21 @@ def gm_distance_nc(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, out=
     x / ||x|| and (x - mean) / ||x - mean||, so that a map and a scaled copy of it are at distance 0 (exactly +0.0 for a power of
     two) and every term lies in [0, 2]. A map with nothing to normalise (all zeros; under "correlation" any constant map) counts
     as the zero map: distance 1 to every other map, exactly 0 to the other flat ones, so dead channels score low.
+    lowpass=K > 0 takes the distance between the maps' low-pass signatures instead, d_K(a, b) = ||P_K DCT(a) - P_K DCT(b)||_2
+    with P_K the K x K lowest frequencies of the orthonormal DCT (lowpass_nc; K >= max(H, W) is the plain distance up to
+    rounding): two maps that share their coarse structure and differ in fine texture or noise are then close. The signatures
+    of the channel hull of the two ranges are computed once and this function runs on them: "l2" as it is; "cosine" on the
+    unit signatures; "correlation" as "cosine" on the signatures without their DC term (drop_dc: the mean of a map is its DC
+    coefficient, so the centring is the dropped term), where a flat map is the zero map as above. Everything exact above holds
+    of the signatures. A map with an edge below K keeps all its coefficients along that edge. A non-flat map whose low band
+    is empty (all its structure above K) is compared by what its signature holds: round-off under a metric, which normalises
+    it. The signature pass runs on every call, over the whole hull: scoring a layer in several channel ranges against the
+    same reference set repeats it per range (same bits; a caller that minds computes lowpass_nc once and passes the
+    signatures). ValueError for K < 0, and for K = 1 under "correlation" (nothing is left). lowpass=0 is the call it always was.
     float32 NCHW only; a tensor whose maps are not dense (stride(3) != 1 or stride(2) != W) is copied with .contiguous()
     first. Enqueues on the current stream of x's device; no synchronisation."""
+    if lowpass:
+        return _gm_lowpass(gm_distance_nc, x, lowpass, c_begin, c_count, ref_begin, ref_count, metric, out)
     if metric not in GM_METRICS:
         raise ValueError("metric must be one of %s, got %r" % (", ".join(GM_METRICS), metric))
     x, c_begin, c_count, out, stream = _open(x, c_begin, c_count, out, rows="dense")
@@ -384,7 +455,7 @@ def gm_distance_nc(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, out=
     return out
 
 
-def gm_pair_matrix(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, metric="l2", out=None):
+def gm_pair_matrix(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, metric="l2", out=None, lowpass=0):
     """D[j, k] = sum_n d(x[n, c_begin+j], x[n, ref_begin+k]) -> [c_count, ref_count] fp32 (ref_count None = to the end).
 
     The pair matrix of the geometric-median criterion (dcts_gm_pairs_f32): the terms gm_distance_nc adds up over the reference
@@ -394,7 +465,11 @@ def gm_pair_matrix(x, c_begin=0, c_count=None, ref_begin=0, ref_count=None, metr
     against the same reference set are the rows of the whole matrix bit for bit. Selection rules on it are host arithmetic
     (dct_pruning_amd.pairs).
     float32 NCHW only; a tensor whose maps are not dense is copied with .contiguous() first. `out`: a contiguous float32
-    [c_count, ref_count] tensor on x's device to overwrite. Enqueues on the current stream of x's device; no synchronisation."""
+    [c_count, ref_count] tensor on x's device to overwrite. lowpass=K > 0: the distances between the maps' low-pass signatures,
+    composed as gm_distance_nc composes them (same rules, same errors); lowpass=0 is the call it always was.
+    Enqueues on the current stream of x's device; no synchronisation."""
+    if lowpass:
+        return _gm_lowpass(gm_pair_matrix, x, lowpass, c_begin, c_count, ref_begin, ref_count, metric, out)
     if metric not in GM_METRICS:
         raise ValueError("metric must be one of %s, got %r" % (", ".join(GM_METRICS), metric))
     x, c_begin, c_count, _, stream = _open(x, c_begin, c_count, out=False, rows="dense")

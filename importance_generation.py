@@ -14,7 +14,9 @@ under entropy_score/, or every map's summed distance to the other maps of its la
 gm_score/; --gm_metric {l2,cosine,correlation} takes that distance between the maps as they are or between unit maps, which
 go to gm_score/<net>_limit<L>_<metric>/, and --gm_pairs writes the [c, c] matrix of mean pair distances per file instead of its
 row sums, to gm_score/<net>_limit<L>[_<metric>]_pairs/, which `python -m dct_pruning_amd.pairs --matrix DIR --rule
-{sum,nn,kcenter} --out DIR2` turns into imp_*.npy on the host), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
+{sum,nn,kcenter} --out DIR2` turns into imp_*.npy on the host, and --gm_lowpass K takes every distance between the maps' K x K
+lowest DCT coefficients instead of the maps, to gm_score/<net>_limit<L>[_<metric>]_low<K>[_pairs]/; a speed-up for the six
+classification nets, a slow-down for u2netp, whose hook shapes have no fused signature kernel), --autocast {fp16,bf16} (the forward sweeps run under torch.autocast and the
 half-precision feature maps are scored as they are) and --channels_last (the net and its inputs run in
 torch.channels_last and the feature maps are scored in the layout they arrive in). dct_pruning_amd/harness.py says
 what each criterion writes and which of these modes and nets it supports (its criterion table and check_options, which
@@ -66,6 +68,12 @@ def parse_args(argv=None):
                         help="--criterion gm: write the [c, c] matrix of mean pair distances per file instead of its row sums "
                              "(gm_score/<net>_limit<L>[_<metric>]_pairs/); python -m dct_pruning_amd.pairs turns it into "
                              "imp_*.npy under a selection rule (sum, nn, kcenter)")
+    parser.add_argument("--gm_lowpass", type=int, default=0,
+                        help="--criterion gm: compare the K x K lowest DCT coefficients of the maps instead of the maps, so that "
+                             "maps which share their coarse structure are close (0: whole maps; not 1 with correlation; "
+                             "gm_score/<net>_limit<L>[_<metric>]_low<K>[_pairs]/). Fast for square maps of edge <= 64 that "
+                             "have a codelet; other shapes (u2netp's 72 ... 288) take the dct2d coefficient path and run "
+                             "SLOWER than plain gm")
     parser.add_argument("--autocast", type=str, default=None, choices=("fp16", "bf16"),
                         help="run the forward sweeps under torch.autocast and score the half-precision feature maps natively")
     parser.add_argument("--channels_last", action="store_true",
@@ -73,7 +81,8 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     try:
         harness.check_options(args.criterion, args.net, args.deferred, args.autocast, args.channels_last,
-                              (args.bands, args.band_kind), gm_metric=args.gm_metric, gm_pairs=args.gm_pairs)
+                              (args.bands, args.band_kind), gm_metric=args.gm_metric, gm_pairs=args.gm_pairs,
+                              gm_lowpass=args.gm_lowpass)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -129,7 +138,8 @@ def main(argv=None):
     harness.imp_score(net, args, single_sweep=args.single_sweep,
                       accumulate="device" if args.device_accumulate else "host", deferred=args.deferred,
                       criterion=args.criterion, bands=(args.bands, args.band_kind), autocast=args.autocast,
-                      channels_last=args.channels_last, gm_metric=args.gm_metric, gm_pairs=args.gm_pairs)
+                      channels_last=args.channels_last, gm_metric=args.gm_metric, gm_pairs=args.gm_pairs,
+                      gm_lowpass=args.gm_lowpass)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -51,7 +51,8 @@ extern "C" {
  *    (dcts_spectral_entropy_f32, dcts_entropy_workspace_bytes, dcts_has_entropy_kernel), and for the geometric-median
  *    criterion's entry point (dcts_gm_distance_f32) and its normalised metrics (dcts_gm_distance_metric_f32,
  *    dcts_gm_workspace_bytes, DCTS_GM_*) and its pair matrix (dcts_gm_pairs_f32, dcts_gm_pairs_workspace_bytes,
- *    dcts_gm_pairs_slices). */
+ *    dcts_gm_pairs_slices), and for the low-pass signature (dcts_dct2d_lowpass_f32, dcts_dct2d_lowpass_workspace_bytes,
+ *    DCTS_LOWPASS_DROP_DC). */
 #define DCTS_ABI_VERSION 3
 
 enum {
@@ -362,6 +363,42 @@ int dcts_gm_pairs_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int
                       int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
                       int32_t c_begin, int32_t c_count, int32_t r_begin, int32_t r_count,
                       float* out_cr, void* stream, int32_t metric, void* workspace, size_t workspace_bytes);
+
+/*
+ * The low-pass DCT signature of every map (lowpass.hip): the corner of the lowest frequencies of dcts_dct2d_f32's output,
+ *
+ *     out[((n*c_count + j)*Kh + u)*Kw + v] = dct_2d(x[n, c_begin+j], norm='ortho')[u][v],   u < Kh = min(K, H), v < Kw = min(K, W)
+ *
+ * [N, c_count, Kh, Kw] fp32, dense, and nothing else: a map is read once and Kh*Kw floats are written. The distance between
+ * two signatures, || P_K DCT(a) - P_K DCT(b) ||_2, is the band-limited form of the distance dcts_gm_distance_f32 takes (which
+ * the orthonormal transform leaves unchanged when every coefficient is kept): the gm entry points take `out` as their tensor.
+ *   x, strides, c_begin, c_count    as for dcts_energy_f32 (strideW == 1, strideH >= W). There is no odd front pad.
+ *   K          >= 1 (DCTS_E_SHAPE otherwise). An edge shorter than K keeps all its coefficients: Kh = H, Kw = W there.
+ *   flags      0, or DCTS_LOWPASS_DROP_DC; any other bit: DCTS_E_UNSUPPORTED. With DCTS_LOWPASS_DROP_DC, out[.., 0, 0] is
+ *              written as +0.0 (the signature of the centred map), and a FLAT map - every element equal to the first, all-zero
+ *              maps included - gets an all-+0.0 signature. The test is made on the map itself and is exact: the AC coefficients of
+ *              a constant map are exactly 0 for power-of-two edges only, and the round-off the other edges leave there would,
+ *              normalised, be a unit vector of noise. A map that holds a NaN is not flat. Every other element has the bits it
+ *              has without the flag.
+ *   workspace  device memory, 16-byte aligned, at least dcts_dct2d_lowpass_workspace_bytes(N, c_count, H, W, K) bytes. That is 0
+ *              for dense square maps of an edge dcts_has_codelet names, which one fused launch serves (NULL is fine). Every
+ *              other shape up to DCTS_MAX_EDGE takes the coefficient path of dcts_dct2d_f32 chunk by chunk into the workspace
+ *              and a gather of the corners; so does a codelet shape whose rows have a pitch: size its workspace as for
+ *              (H, W + 1), which is never fused and never needs less. The call overwrites the workspace; one shared with the
+ *              other entry points is handled as theirs (dcts_workspace_invalidate[_range]).
+ *   Checks, in this order: everything dcts_energy_f32 checks, in its order; K; flags; then, on the fallback only, the workspace
+ *              (NULL or too small: DCTS_E_WORKSPACE; not 16-byte aligned: DCTS_E_ALIGN). All before any launch.
+ * A map's signature depends on that map alone: the same bits for any N, channel slice, position in a wave, chunk or launch
+ * count; no atomics; a NaN map touches only its own signature. On the fallback the signature is the corner of dcts_dct2d_f32's
+ * output bit for bit; the fused kernel's agrees with it to the kernels' rounding (2e-6 of the largest coefficient).
+ * Only enqueues on `stream`; no host state beyond the workspace memo of the other entry points.
+ */
+#define DCTS_LOWPASS_DROP_DC 1
+size_t dcts_dct2d_lowpass_workspace_bytes(int64_t N, int32_t c_count, int64_t H, int64_t W, int32_t K);
+int dcts_dct2d_lowpass_f32(const float* x, int64_t N, int64_t C_total, int64_t H, int64_t W,
+                           int64_t strideN, int64_t strideC, int64_t strideH, int64_t strideW,
+                           int32_t c_begin, int32_t c_count, int32_t K, int32_t flags,
+                           float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * dcts_energy_f32 for feature maps of another element type: what a forward pass under autocast hands to a hook.
