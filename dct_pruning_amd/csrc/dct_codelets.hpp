@@ -23,7 +23,17 @@
 //            X[2j] = A[j] + B[M1-j], X[2j-1] = A[j] - B[M1-j]   (0 < j < M1)
 //            (rotations are orthogonal and the tail is add/sub only: numerically stable)
 //   odd N  : direct, using the x[n] <-> x[N-1-n] symmetry (about N^2/2 FMAs)
-//   DCT-IV odd M : direct M x M.
+//   DCT-IV odd M >= 5 : with a = 2n+1, b = 2k+1 and gcd(8, M) = 1 the angle splits (CRT):
+//            pi a b / (4M) = t pi/4 + 2 pi n' k' / M  (mod 2 pi),
+//            n' = a mod M, k' = (8^-1 mod M) b mod M, t = a b (M^-1 mod 8) mod 8 (odd),
+//            cos(phi + t pi/4) = (chi_c(t) cos phi - chi_s(t) sin phi) / sqrt 2, chi_c, chi_s = +-1 and
+//            multiplicative in t. With pc[n'] = chi_c(a) v[n], ps[n'] = chi_s(a) v[n], u = M^-1 mod 8:
+//            X[k] = chi_c(b) chi_c(u) C[k'] - chi_s(b) chi_s(u) S[k'],
+//            C[k'] = sum pc[n'] cos(2 pi n' k'/M) / sqrt 2,  S[k'] = sum ps[n'] sin(2 pi n' k'/M) / sqrt 2.
+//            C[M-k'] = C[k'], S[M-k'] = -S[k'], S[0] = 0: pre-sums pc[j] + pc[M-j], ps[j] - ps[M-j],
+//            rows k' = 0..(M-1)/2 only, one add or sub per output: about M^2/2 (M = 7: 34 against 49).
+//            Signs and permutations are compile-time: add/sub choices and literals.
+//   DCT-IV M = 3 : direct 3 x 3 (the split form saves nothing there).
 //
 // This header is plain C++17 and is also compiled for the host by the CPU test-suite
 // (tests/native/codelet_host.cpp) so the algebra is checked without a GPU.
@@ -80,6 +90,26 @@ constexpr double cospi_frac(long long p, long long q) {
 constexpr double sinpi_frac(long long p, long long q) {  // sin(pi p/q) = cos(pi (q - 2p) / (2q))
   return cospi_frac(q - 2 * p, 2 * q);
 }
+
+// index arithmetic of the odd-length DCT-IV (Dct4, odd M >= 5)
+constexpr int inv_mod(int a, int q) {  // a^-1 mod q, gcd(a, q) = 1
+  for (int x = 1; x < q; ++x)
+    if ((a * x) % q == 1) return x;
+  return 0;
+}
+constexpr int odd_index(int j, int M) {  // the n < M with 2n+1 = j (mod M), M odd
+  for (int n = 0; n < M; ++n)
+    if ((2 * n + 1) % M == j) return n;
+  return -1;
+}
+constexpr int out_index(int kp, int M, int w) {  // the k < M with w (2k+1) = kp (mod M)
+  for (int k = 0; k < M; ++k)
+    if ((w * (2 * k + 1)) % M == kp) return k;
+  return -1;
+}
+// sqrt(2) cos(t pi/4) and sqrt(2) sin(t pi/4) for odd t: the two real characters mod 8 other than (-1/t)
+constexpr int chi_c(int t) { return (t % 8 == 1 || t % 8 == 7) ? 1 : -1; }
+constexpr int chi_s(int t) { return (t % 8 == 1 || t % 8 == 3) ? 1 : -1; }
 
 // compile-time loop: f(std::integral_constant<int, I>{}) for I in [0, N)
 template <class F, int... I>
@@ -172,7 +202,8 @@ struct Dct4 {
         X[2 * j] = A[j] + B[H - j];
         X[2 * j - 1] = A[j] - B[H - j];
       });
-    } else {
+    } else if constexpr (M == 3) {
+      // the split form below saves nothing at M = 3 (9 against 9) and costs registers: direct sum
       static_for<M>([&](auto ik) DCTS_LAMBDA_INLINE {
         constexpr int k = decltype(ik)::value;
         T acc{};
@@ -185,6 +216,95 @@ struct Dct4 {
             acc += v[n] * c;
         });
         X[k] = acc;
+      });
+    } else {
+      // odd M >= 5: pi a b / (4M) = t pi/4 + 2 pi n' k' / M (header comment). Every sign below is a
+      // compile-time choice between + and -, or sits in a literal; nothing is multiplied by +-1.
+      constexpr int m = (M - 1) / 2;
+      constexpr int u = inv_mod(M % 8, 8), w = inv_mod(8 % M, M);
+      constexpr double r = cospi_frac(1, 4);  // 1/sqrt(2)
+      // The order of the statements is chosen by the compiler's register count: the sine half first
+      // (pre-sums d, rows Sg), then the cosine half, each cosine row finishing its two outputs at once.
+      // d[j-1] = chi_s(a1) (ps[j] - ps[M-j]),  s[j-1] = chi_c(a1) (pc[j] + pc[M-j]),  a1 = 2 n1 + 1 = j (mod M);
+      // the factors chi_s(a1), chi_c(a1) go into the literals of the rows
+      T d[m];
+      static_for<m>([&](auto ij) DCTS_LAMBDA_INLINE {
+        constexpr int j = decltype(ij)::value + 1;
+        constexpr int n1 = odd_index(j, M), n2 = odd_index(M - j, M);
+        if constexpr (chi_s(2 * n1 + 1) == chi_s(2 * n2 + 1))
+          d[j - 1] = v[n1] - v[n2];
+        else
+          d[j - 1] = v[n1] + v[n2];
+      });
+      // row k' has two outputs, w b = k' (kA) and w b = -k' (kB) (mod M). With al = chi_c(b) chi_c(u) and
+      // be = chi_s(b) chi_s(u) at each:  Sg[k'-1] = alA beA S[k'], C = C[k'], X[kA] = alA (C - Sg), X[kB] = alB (C + Sg)
+      T Sg[m];
+      static_for<m>([&](auto ik) DCTS_LAMBDA_INLINE {
+        constexpr int kp = decltype(ik)::value + 1;
+        constexpr int kA = out_index(kp, M, w), kB = out_index(M - kp, M, w);
+        constexpr int abA = chi_c(2 * kA + 1) * chi_c(u) * chi_s(2 * kA + 1) * chi_s(u);
+        constexpr int abB = chi_c(2 * kB + 1) * chi_c(u) * chi_s(2 * kB + 1) * chi_s(u);
+        // 2 kA + 1 + 2 kB + 1 = 2M = 2 (mod 4): chi_c chi_s is the same at both outputs
+        static_assert(abA == abB, "odd DCT-IV: sign pairing");
+        static_for<m>([&](auto ij) DCTS_LAMBDA_INLINE {
+          constexpr int j = decltype(ij)::value + 1;
+          constexpr int a1 = 2 * odd_index(j, M) + 1;
+          constexpr float ss = float(abA * chi_s(a1) * r * sinpi_frac(2 * j * kp, M));
+          if constexpr (j == 1)
+            Sg[kp - 1] = d[0] * ss;
+          else
+            Sg[kp - 1] += d[j - 1] * ss;
+        });
+      });
+      T s[m];
+      static_for<m>([&](auto ij) DCTS_LAMBDA_INLINE {
+        constexpr int j = decltype(ij)::value + 1;
+        constexpr int n1 = odd_index(j, M), n2 = odd_index(M - j, M);
+        if constexpr (chi_c(2 * n1 + 1) == chi_c(2 * n2 + 1))
+          s[j - 1] = v[n1] + v[n2];
+        else
+          s[j - 1] = v[n1] - v[n2];
+      });
+      // n' = 0 is the middle sample (a = M); it enters every cosine row with cos 0 = 1
+      constexpr float r0 = float(chi_c(M) * r);
+      const T t0 = v[m] * r0;
+      {  // k' = 0: one output, b = M, no sine part
+        constexpr int k = odd_index(0, M);
+        constexpr int al = chi_c(2 * k + 1) * chi_c(u);
+        constexpr int g1 = chi_c(2 * odd_index(1, M) + 1);
+        T sum = s[0];
+        static_for<m - 1>([&](auto ij) DCTS_LAMBDA_INLINE {
+          constexpr int j = decltype(ij)::value + 2;
+          if constexpr (chi_c(2 * odd_index(j, M) + 1) == g1)
+            sum += s[j - 1];
+          else
+            sum -= s[j - 1];
+        });
+        constexpr float rg = float(g1 * r);
+        if constexpr (al > 0)
+          X[k] = sum * rg + t0;
+        else
+          X[k] = sum * (-rg) - t0;
+      }
+      static_for<m>([&](auto ik) DCTS_LAMBDA_INLINE {
+        constexpr int kp = decltype(ik)::value + 1;
+        constexpr int kA = out_index(kp, M, w), kB = out_index(M - kp, M, w);
+        constexpr int alA = chi_c(2 * kA + 1) * chi_c(u), alB = chi_c(2 * kB + 1) * chi_c(u);
+        T C = t0;
+        static_for<m>([&](auto ij) DCTS_LAMBDA_INLINE {
+          constexpr int j = decltype(ij)::value + 1;
+          constexpr int a1 = 2 * odd_index(j, M) + 1;
+          constexpr float cc = float(chi_c(a1) * r * cospi_frac(2 * j * kp, M));
+          C += s[j - 1] * cc;
+        });
+        if constexpr (alA > 0)
+          X[kA] = C - Sg[kp - 1];
+        else
+          X[kA] = Sg[kp - 1] - C;
+        if constexpr (alB > 0)
+          X[kB] = C + Sg[kp - 1];
+        else
+          X[kB] = -C - Sg[kp - 1];
       });
     }
   }
