@@ -4,8 +4,9 @@
 HostAccumulator   reference-exact: per-map energies come back to the host and the SAME torch
                   CPU ops as the reference run on them (view/sum(0), three-rounding mean).
 DeviceAccumulator the fused device form (dcts_running_mean_update_f32): nothing leaves the
-                  GPU until the scores are read; same rounding sequence, batch sum in
-                  ascending n instead of torch's pairwise sum(0).
+                  GPU until the scores are read; same rounding sequence, batch sum in the
+                  16-slice order of include/dctscore.h (slice s adds n = s, s+16, ... ascending, the
+                  partials are added in slice order) instead of torch's pairwise sum(0).
 DeviceBatchAccumulator  many hook points at once (single-sweep harness): the per-layer updates of
                   a batch are deferred and issued as ONE launch
                   (dcts_running_mean_update_multi_f32) when the next batch starts or the

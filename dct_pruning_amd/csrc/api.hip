@@ -961,16 +961,19 @@ int dcts_energy_mixed_f32(const dcts_shaped_item* items, int32_t count, void* wo
 int dcts_running_mean_update_multi_f32(const dcts_update_desc* descs, int32_t count, void* stream) {
   if (!descs) return DCTS_E_NULL;
   if (count <= 0) return DCTS_E_SHAPE;
+  // every descriptor before the first launch: the update is in place, so a refusal after a chunk had been enqueued would
+  // leave that chunk's feature_result advanced under a caller that keeps its totals and retries
+  for (const dcts_update_desc* d = descs; d < descs + count; ++d) {
+    if (!d->energy_nc || !d->feature_result) return DCTS_E_NULL;
+    if (d->N <= 0 || d->C_count <= 0) return DCTS_E_SHAPE;
+  }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int rc = DCTS_OK;  // of the last launch that failed: every chunk is launched (and checked only when its turn comes)
+  int rc = DCTS_OK;  // of the last launch that failed: every chunk is launched
   for (int32_t i0 = 0; i0 < count; i0 += kMultiMax) {
     const int n = (count - i0) < kMultiMax ? (count - i0) : kMultiMax;
     int64_t cmax = 0;
-    for (const dcts_update_desc* d = descs + i0; d < descs + i0 + n; ++d) {
-      if (!d->energy_nc || !d->feature_result) return DCTS_E_NULL;
-      if (d->N <= 0 || d->C_count <= 0) return DCTS_E_SHAPE;
+    for (const dcts_update_desc* d = descs + i0; d < descs + i0 + n; ++d)
       if (d->C_count > cmax) cmax = d->C_count;
-    }
     if (const int r = launch_running_mean_multi(descs + i0, n, cmax, st)) rc = r;
   }
   return rc;

@@ -62,6 +62,18 @@ __global__ __launch_bounds__(kSumCh * kSumSl) void k_batch_sum(const float* __re
   if (slice == 0 && j < C) out_c[j] = t;
 }
 
+// (fr * total + t) / (total + n) in the reference's three fp32 roundings: product, sum, quotient. Plain operators under
+// contract(off), not __fadd_rn(__fmul_rn(..), ..): the HIP headers define those two as `*` and `+`, and once they are
+// inlined the default -ffp-contract=fast turns the pair into one v_fmac_f32 - a single rounding, other bits than the
+// reference's in about a tenth of the channels (tests/test_reduce_gpu.py compares the bits). The division stays correctly rounded.
+__device__ __forceinline__ float mean_update(float fr, float total, float t, float n) {
+#pragma clang fp contract(off)
+  const float prod = fr * total;
+  const float acc = prod + t;
+  const float den = total + n;
+  return __fdiv_rn(acc, den);
+}
+
 // fr[j] <- (fr[j] * total + sum_n e[n*C + j]) / (total + N): the running-mean update of
 // utils/common.py:274-277 fused with the batch sum of :273 (same three fp32 roundings)
 __global__ __launch_bounds__(kSumCh * kSumSl) void k_running_mean(const float* __restrict__ e, long long N,
@@ -71,10 +83,7 @@ __global__ __launch_bounds__(kSumCh * kSumSl) void k_running_mean(const float* _
   const int slice = threadIdx.x / kSumCh;
   const long long j = (long long)blockIdx.x * kSumCh + threadIdx.x % kSumCh;
   const float t = strip_batch_sum(e, N, C, j, slice, part);
-  if (slice == 0 && j < C) {
-    const float acc = __fadd_rn(__fmul_rn(fr[j], total), t);
-    fr[j] = __fdiv_rn(acc, __fadd_rn(total, float(N)));
-  }
+  if (slice == 0 && j < C) fr[j] = mean_update(fr[j], total, t, float(N));
 }
 
 // the same update for up to kMultiMax hook points in one launch (descriptors by value in the
@@ -89,10 +98,7 @@ __global__ __launch_bounds__(kSumCh * kSumSl) void k_running_mean_multi(UpdateBa
   const int slice = threadIdx.x / kSumCh;
   const long long j = (long long)blockIdx.x * kSumCh + threadIdx.x % kSumCh;
   const float t = strip_batch_sum(d.energy_nc, d.N, d.C_count, j, slice, part);
-  if (slice == 0 && j < d.C_count) {
-    const float acc = __fadd_rn(__fmul_rn(d.feature_result[j], d.total_before), t);
-    d.feature_result[j] = __fdiv_rn(acc, __fadd_rn(d.total_before, float(d.N)));
-  }
+  if (slice == 0 && j < d.C_count) d.feature_result[j] = mean_update(d.feature_result[j], d.total_before, t, float(d.N));
 }
 
 // Score variant in the coefficient domain: out[m] = sum_{u,v} weights[u,v] * coeff[m][u][v]^2.

@@ -186,7 +186,9 @@ def dct2d(x, c_begin=0, c_count=None, pad_front_if_odd=False, algo=ALGO_AUTO):
 
 
 def batch_sum(energy):
-    """out[j] = sum_n energy[n, j], n ascending (fused variant for the bench / single-sweep mode)."""
+    """out[j] = sum_n energy[n, j] in the fixed order of dcts_batch_sum_f32 (include/dctscore.h): 16 interleaved slices,
+    slice s adds n = s, s+16, ... ascending, then the 16 partial sums are added in slice order (fused variant for the
+    bench / single-sweep mode; tests/reduce_oracle.py states the order in numpy)."""
     if energy.dim() != 2 or energy.dtype != torch.float32 or not energy.is_cuda:
         raise ValueError("expected a float32 CUDA tensor [N, C]")
     energy = energy.contiguous()

@@ -521,6 +521,9 @@ int dcts_running_mean_update_f32(const float* energy_nc, int64_t N, int64_t C_co
  * The same update for `count` hook points in ONE launch (single-sweep harness: every layer's
  * energies of a batch are ready when the forward pass ends). `descs` is a HOST array; it is
  * copied into the kernel arguments, so it may be reused as soon as the call returns.
+ * Every descriptor is checked before anything is enqueued: a negative return leaves every
+ * feature_result untouched, so the caller may keep its totals and repeat the batch. Two
+ * descriptors of one call must not share a feature_result (their updates are not ordered).
  */
 typedef struct dcts_update_desc {
   const float* energy_nc; /* [N, C_count] device */
