@@ -2,8 +2,8 @@
 // and launch rules (CodeletCfg), and the plain form of the body - lane role, group walk, fp32 column load, both passes
 // through the wave's slab, energy epilogue - that band.hip, entropy.hip, half.hip and nhwc.hip build their kernels from;
 // each of them adds a load or an epilogue of its own. codelet.hip's kernels (the ones bench.py measures) keep their own
-// text of the body and say where they leave the plain form. Host side: the grid rule, the launch helper, the occupancy
-// query and the size switch.
+// text of the body and say where they leave the plain form. Host side: the grid rule, the launch helper and the size
+// switch (the occupancy query blocks_per_cu() is in dcts_internal.h).
 //
 // One wave owns G = floor(64 / N) maps per iteration. Pass 1: lane = column, the lane holds the whole column in VGPRs
 // (row r of a map is one contiguous segment across lanes: coalesced loads straight from HBM) and runs a straight-line
@@ -196,16 +196,6 @@ int launch_codelet_grid(void (*kernel)(P...), long long nmaps, hipStream_t st, c
   const long long ngroups = (nmaps + Cfg::G - 1) / Cfg::G;
   hipLaunchKernelGGL(kernel, dim3(codelet_grid<N>(ngroups)), dim3(64 * Cfg::WAVES), 0, st, args...);
   return (int)hipGetLastError();
-}
-// workgroups of `kernel` (WAVES waves, static LDS only) that fit a CU, queried once: the persistent grids are one residency
-template <auto kernel, int WAVES>
-int blocks_per_cu() {
-  static const int per_cu = [] {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 64 * WAVES, 0) != hipSuccess || n < 1) n = 1;
-    return n;
-  }();
-  return per_cu;
 }
 // f(N, PAD) as integral constants for the edge n of DCTS_CODELET_SIZES; the odd front pad makes an even edge, so the
 // padded variant exists only for even N

@@ -105,6 +105,18 @@ inline int num_cus() {
   return n;
 }
 
+// workgroups of `kernel` (WAVES waves, static LDS only) that fit a CU, queried once: the persistent grids of the codelet and
+// the role-wave families are one residency
+template <auto kernel, int WAVES>
+int blocks_per_cu() {
+  static const int per_cu = [] {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 64 * WAVES, 0) != hipSuccess || n < 1) n = 1;
+    return n;
+  }();
+  return per_cu;
+}
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ---- which shapes a family serves (from the tables of codelet_sizes.h) -----------------------------------------

@@ -50,6 +50,18 @@ struct FusedCfg {
   static_assert(N % 4 == 0, "shape");
 };
 
+// image column `lane` of pass-2 round r holds the H-axis leaf output of this row (-1: a padding column)
+template <int M, int L, int r>
+__device__ __forceinline__ int fused_leaf_row(int lane) {
+  using Cfg = FusedCfg<M, L>;
+  if constexpr (Cfg::BALANCED) {
+    return balanced_leaf_row<M, Cfg::KPR>(lane, r);
+  } else {
+    const int q = lane / M;
+    return (r * Cfg::RPR + q) * M + (lane - q * M);
+  }
+}
+
 // The one-role-per-wave fused kernel with pass 1 on samples loaded into registers and alternating pass-2 buffers (see
 // f2_load_item in split_common.hpp; the staged pass 1 is in git history). Same box, staged -> register loads, % of the
 // HBM peak: 96: 38.1 -> 43.2, 192: 33.0 -> 33.9, 256: 35.3 -> 35.8
@@ -63,36 +75,18 @@ template <int M, int L, int ROLE, bool STORE = false>
 __device__ __forceinline__ void fused_body(const TileBatch& tb, lds_ptr lds, lds_ptr partials, int lane,
                                            float* leaf_out = nullptr) {
   using Cfg = FusedCfg<M, L>;
+  using P1 = F2Pass1<M, L, ROLE, Cfg::S>;  // this wave's butterfly items: p = ROLE, ROLE + S, ...
   constexpr int N = Cfg::N, S = Cfg::S, SW = Cfg::SW, STRIPS = Cfg::STRIPS, COLS = Cfg::COLS, KPR = Cfg::KPR,
                 RPR = Cfg::RPR, ROUNDS = Cfg::ROUNDS, RW = Cfg::RW, BUF = Cfg::BUF;
   int cur = 0, pslot = 0, pending_slot = 0;
   long long pending_m = -1;
   long long m = blockIdx.x;
-#ifdef DCTS_FUSED_STAMPS
-  unsigned long long acc_[16] = {}, last_;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(last_)::"memory");
-#endif
+  DCTS_STAMP_BEGIN();
   const long long nmaps = tb.total;
   int hint_in = 0, hint_next = 0, hint_out = 0;  // tensor of the current / next / finished map (tile_item)
-  constexpr int ITEMS = ROLE < M ? (M - ROLE + S - 1) / S : 0;  // this wave's butterfly items p = ROLE, ROLE + S, ...
-  static_assert(ITEMS <= ROUNDS, "one item of the next map per pass-2 round");
-  float pre[ITEMS > 0 ? ITEMS : 1][1 << L];
-  auto map_rsrc = [&](const float* base, bool valid) DCTS_LAMBDA_INLINE {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, valid ? (unsigned)(N * N * 4) : 0u, 0x00020000);
-  };
-  auto lane_voff = [&](int strip) DCTS_LAMBDA_INLINE {
-    const int ln = launder(lane);
-    return (strip * SW + ln < N) ? ln * 4 : kLaneOut;
-  };
-  if (m < nmaps) {
-    const float* first = tile_in(tb, m);
-    const __amdgpu_buffer_rsrc_t rs = map_rsrc(first, true);
-    const int vo = lane_voff(0);
-    dcts::static_for<ITEMS>([&](auto ii) DCTS_LAMBDA_INLINE {
-      constexpr int i = decltype(ii)::value;
-      f2_load_item<M, L, ROLE + S * i, 0>(rs, vo, pre[i]);
-    });
-  }
+  static_assert(P1::ITEMS <= ROUNDS, "one item of the next map per pass-2 round");
+  typename P1::Pre pre;
+  if (m < nmaps) DCTS_F2_FIRST_STRIP(ROLE, S, tile_in(tb, m), lane, pre)
   for (; m < nmaps; m += gridDim.x) {
     const float* in_b = tile_in(tb, m, &hint_in);
     float parked[STRIPS][M];
@@ -105,22 +99,13 @@ __device__ __forceinline__ void fused_body(const TileBatch& tb, lds_ptr lds, lds
       const int ln = launder(lane);
       const bool act = s * SW + ln < N;
       DCTS_STAMP(2);
-      {
-        const __amdgpu_buffer_rsrc_t rs = map_rsrc(in_b, true);
-        const int vo = (s + 1 < STRIPS) ? lane_voff(s + 1) : 0;
-        dcts::static_for<ITEMS>([&](auto ii) DCTS_LAMBDA_INLINE {
-          constexpr int i = decltype(ii)::value;
-          f2_network_store<M, L, ROLE + S * i>(pre[i], buf, SW, ln, act);
-          if constexpr (s + 1 < STRIPS) f2_load_item<M, L, ROLE + S * i, (s + 1 < STRIPS ? s + 1 : 0)>(rs, vo, pre[i]);
-          __builtin_amdgcn_sched_barrier(0);
-        });
-      }
+      DCTS_F2_STRIP(ROLE, S, s, in_b, buf, lane, ln, act, pre)
       DCTS_STAMP(3);
       lds_barrier();
       DCTS_STAMP(4);
       if constexpr (s == 0) {
         if (pending_m >= 0) {
-          if constexpr (!STORE) fused_finish<M, L, ROLE>(partials, pending_slot, pending_m, tb, lane, &hint_out);
+          if constexpr (!STORE) fused_finish<M, L, S, ROLE>(partials, pending_slot, pending_m, tb, lane, &hint_out);
           pending_m = -1;
         }
       }
@@ -130,7 +115,7 @@ __device__ __forceinline__ void fused_body(const TileBatch& tb, lds_ptr lds, lds
     });
     // ---- pass 2: W axis, RPR role groups of parked rows per round ---------------------------
     const lds_ptr blk0 = lds + (cur ^ 1) * BUF;  // the last strip's buffer; the other one is free
-    const lds_ptr blk1 = lds + cur * BUF;          // rounds alternate between the buffers: two barriers per round (see fused2_body)
+    const lds_ptr blk1 = lds + cur * BUF;          // rounds alternate between the buffers: two barriers per round (see fused2.hip)
     float e = 0.f;
     dcts::static_for<ROUNDS>([&](auto ir) DCTS_LAMBDA_INLINE {
       constexpr int r = decltype(ir)::value;
@@ -139,19 +124,7 @@ __device__ __forceinline__ void fused_body(const TileBatch& tb, lds_ptr lds, lds
       if constexpr (r == 0) lds_barrier();  // previous readers of blk are done
       DCTS_STAMP(6);
       if constexpr (Cfg::BALANCED) {
-        dcts::static_for<STRIPS>([&](auto is) DCTS_LAMBDA_INLINE {
-          constexpr int s = decltype(is)::value;
-          const int line = s * SW + lane;
-          const int off = (line < N ? line : 0) * RW + ROLE * KPR;
-          dcts::static_for<KPR>([&](auto ik) DCTS_LAMBDA_INLINE {
-            constexpr int k = decltype(ik)::value;
-            if constexpr (r * KPR + k < M) {
-              if (line < N) blk[off + k] = parked[s][r * KPR + k];
-            } else {
-              if (line < N) blk[off + k] = 0.f;  // padding column: contributes exactly zero energy
-            }
-          });
-        });
+        DCTS_DUMP_BALANCED(ROLE, STRIPS, r, blk, lane, parked[s][k])
       } else if constexpr (ROLE / RPR == r) {
         dcts::static_for<STRIPS>([&](auto is) DCTS_LAMBDA_INLINE {
           constexpr int s = decltype(is)::value;
@@ -164,10 +137,7 @@ __device__ __forceinline__ void fused_body(const TileBatch& tb, lds_ptr lds, lds
         });
       }
       DCTS_STAMP(7);
-      if constexpr (r < ITEMS) {  // item r of the next map's first strip
-        const __amdgpu_buffer_rsrc_t rs = map_rsrc(next_b, more_maps);
-        f2_load_item<M, L, ROLE + S * (r < ITEMS ? r : 0), 0>(rs, lane_voff(0), pre[r < ITEMS ? r : 0]);
-      }
+      DCTS_F2_NEXT_MAP_ITEM(ROLE, S, r, next_b, more_maps, lane, pre)
       lds_barrier();
       DCTS_STAMP(8);
       // columns of this round: all of them, or fewer whole roles in the last unbalanced round
@@ -177,28 +147,7 @@ __device__ __forceinline__ void fused_body(const TileBatch& tb, lds_ptr lds, lds
       DCTS_STAMP(9);
       lds_barrier();
       DCTS_STAMP(10);
-      float o[M];
-      split_role_transform<M, L, ROLE>(blk + (act ? lane : 0), RW, o);
-      if constexpr (STORE) {
-        // image column `lane` of round r holds the H-axis leaf output iH
-        int iH;
-        if constexpr (Cfg::BALANCED) {
-          const int q = lane / KPR, kh = r * KPR + (lane - q * KPR);
-          iH = kh < M ? q * M + kh : -1;  // padding columns
-        } else {
-          const int q = lane / M;
-          iH = (r * RPR + q) * M + (lane - q * M);
-        }
-        if (act && iH >= 0) {
-          float* dst = leaf_out + ((long long)m * N + iH) * N + ROLE * M;
-          dcts::static_for<M>([&](auto ik) DCTS_LAMBDA_INLINE { dst[decltype(ik)::value] = o[decltype(ik)::value]; });
-        }
-      }
-      float er = 0.f;
-      dcts::static_for<M>([&](auto ik) DCTS_LAMBDA_INLINE {
-        constexpr int k = decltype(ik)::value;
-        er = fmaf(o[k], o[k], er);
-      });
+      DCTS_ROUND_TAIL(ROLE, STORE, blk + (act ? lane : 0), RW, act, (fused_leaf_row<M, L, r>(lane)), leaf_out, m, o, er)
       if (act) e += er;
       DCTS_STAMP(12);
     });
@@ -216,12 +165,9 @@ __device__ __forceinline__ void fused_body(const TileBatch& tb, lds_ptr lds, lds
   }
   if (pending_m >= 0) {
     lds_barrier();
-    if constexpr (!STORE) fused_finish<M, L, ROLE>(partials, pending_slot, pending_m, tb, lane, &hint_out);
+    if constexpr (!STORE) fused_finish<M, L, S, ROLE>(partials, pending_slot, pending_m, tb, lane, &hint_out);
   }
-#ifdef DCTS_FUSED_STAMPS
-  if (lane == 0)
-    for (int i = 0; i < 16; ++i) atomicAdd(&g_fused_stamps[ROLE][i], acc_[i]);
-#endif
+  DCTS_STAMP_END(ROLE, lane);
 }
 
 template <int M, int L, bool STORE, int... R>
@@ -250,26 +196,10 @@ __global__ __launch_bounds__((64 << L), (fused_waves_per_simd<M, L>())) void k_s
 template <int M, int L>
 int launch_fused(const TileBatch& tb, hipStream_t st) {
   // persistent grid: exactly the workgroups one residency holds (LDS- or register-limited)
-  static const int per_cu = [] {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_split_fused<M, L>, 64 << L, 0) != hipSuccess || n < 1)
-      n = 1;
-    return n;
-  }();
-  const long long cap = (long long)num_cus() * per_cu;
+  const long long cap = (long long)num_cus() * blocks_per_cu<k_split_fused<M, L>, (1 << L)>();
   const long long grid = tb.total < cap ? tb.total : cap;
   hipLaunchKernelGGL((k_split_fused<M, L>), dim3((unsigned)grid), dim3(64 << L), 0, st, tb);
   return (int)hipGetLastError();
-}
-
-template <int M, int L>
-int coeff_fused(const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps, hipStream_t st) {
-  auto launch = [st](const TileBatch& tb, float* leaf) {
-    const long long grid = tb.total < num_cus() ? tb.total : num_cus();
-    hipLaunchKernelGGL((k_split_fused_coeff<M, L>), dim3((unsigned)grid), dim3(64 << L), 0, st, tb, leaf);
-    return (int)hipGetLastError();
-  };
-  return run_coeff_chunks(launch, launch_assemble<M, L, true>, M << L, x, nmaps, out, scratch, scratch_maps, st);
 }
 
 }  // namespace
@@ -278,27 +208,15 @@ namespace dctsi {
 
 int dispatch_fused_coeff(int N, const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps,
                          hipStream_t st) {
-#define DCTS_CASE(N_, M_, L_) \
-  case N_:                    \
-    return coeff_fused<M_, L_>(x, nmaps, out, scratch, scratch_maps, st);
-  switch (N) {
-    DCTS_FUSED_TABLE(DCTS_CASE)
-    default:
-      return DCTS_E_UNSUPPORTED;
-  }
-#undef DCTS_CASE
+  DCTS_SWITCH_TABLE(DCTS_FUSED_TABLE, N, [&](auto m, auto l) {
+    constexpr int M = decltype(m)::value, L = decltype(l)::value;
+    return coeff_role_waves<M, L, k_split_fused_coeff<M, L>, (1 << L)>(x, nmaps, out, scratch, scratch_maps, st);
+  })
 }
 
 int dispatch_fused(int N, const TileBatch& tb, hipStream_t st) {
-#define DCTS_CASE(N_, M_, L_) \
-  case N_:                    \
-    return launch_fused<M_, L_>(tb, st);
-  switch (N) {
-    DCTS_FUSED_TABLE(DCTS_CASE)
-    default:
-      return DCTS_E_UNSUPPORTED;
-  }
-#undef DCTS_CASE
+  DCTS_SWITCH_TABLE(DCTS_FUSED_TABLE, N,
+                    [&](auto m, auto l) { return launch_fused<decltype(m)::value, decltype(l)::value>(tb, st); })
 }
 
 }  // namespace dctsi

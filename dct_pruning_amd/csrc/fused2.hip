@@ -17,8 +17,8 @@ namespace {
 // codelet working set at 16 waves x 128 VGPRs (5 strips x 18 parked + ~60). Eight waves own 256
 // VGPRs each: wave w runs roles 2w and 2w+1 one after the other (2 x 5 x 18 = 180 parked values),
 // the butterfly items are shared by the eight waves, the pass-2 dump is the balanced one (KPR
-// coefficients of every role per round). Otherwise the fused kernel above: double-buffered
-// direct-to-LDS staging, LDS-only barriers, deferred workgroup sum. One launch, HBM traffic = the
+// coefficients of every role per round). Otherwise the fused kernel (fused.hip): pass 1 on samples
+// in registers, two alternating LDS images, LDS-only barriers, deferred workgroup sum. One launch, HBM traffic = the
 // input once, instead of the 3x of the two-launch path.
 template <int M, int L>
 struct Fused2Cfg {
@@ -45,6 +45,7 @@ template <int M, int L, int W, bool STORE = false>
 __device__ __forceinline__ void fused2_body(const TileBatch& tb, lds_ptr buf0, lds_ptr buf1, lds_ptr partials,
                                             int lane_in, float* leaf_out = nullptr) {
   using Cfg = Fused2Cfg<M, L>;
+  using P1 = F2Pass1<M, L, W, Cfg::NW>;
   constexpr int N = Cfg::N, NW = Cfg::NW, SW = Cfg::SW, STRIPS = Cfg::STRIPS, KPR = Cfg::KPR,
                 ROUNDS = Cfg::ROUNDS, RW = Cfg::RW, COLS = Cfg::COLS;
   constexpr int R0 = 2 * W, R1 = 2 * W + 1;
@@ -52,40 +53,16 @@ __device__ __forceinline__ void fused2_body(const TileBatch& tb, lds_ptr buf0, l
   long long pending_m = -1;
   long long m = blockIdx.x;
   const long long nmaps = tb.total;
-#ifdef DCTS_FUSED_STAMPS
-  unsigned long long acc_[16] = {}, last_;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(last_)::"memory");
-#endif
+  DCTS_STAMP_BEGIN();
   int hint_in = 0, hint_next = 0, hint_out = 0;  // tensor of the current / next / finished map (tile_item)
+  // (a lambda: with fused_finish called at its three places, which capture tb and hint_out, both listings moved)
   auto finish = [&](lds_ptr part, int slot, long long mm) DCTS_LAMBDA_INLINE {
-    if (W == 0 && lane_in == 0) {
-      float t = 0.f;
-#pragma unroll
-      for (int i = 0; i < NW; ++i) t += part[slot * NW + i];
-      constexpr float sc = float(4.0 / (double(N) * double(N)));
-      if constexpr (!STORE) *tile_out(tb, mm, &hint_out) = t * sc;
-    }
+    if constexpr (!STORE) fused_finish<M, L, NW, W>(part, slot, mm, tb, lane_in, &hint_out);
   };
   // register-load pass 1: this wave's butterfly items are p = W, W + NW, ... (compile time); pre[i] holds item i's samples
-  constexpr int ITEMS = (M - W + NW - 1) / NW;
-  static_assert(ITEMS <= ROUNDS, "one item of the next map per pass-2 round");
-  float pre[ITEMS][1 << L];
-  auto map_rsrc = [&](const float* base, bool valid) DCTS_LAMBDA_INLINE {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, valid ? (unsigned)(N * N * 4) : 0u, 0x00020000);
-  };
-  auto lane_voff = [&](int strip) DCTS_LAMBDA_INLINE {
-    const int lane = launder(lane_in);
-    return (strip * SW + lane < N) ? lane * 4 : kLaneOut;
-  };
-  if (m < nmaps) {
-    const float* first = tile_in(tb, m);
-    const __amdgpu_buffer_rsrc_t rs = map_rsrc(first, true);
-    const int vo = lane_voff(0);
-    dcts::static_for<ITEMS>([&](auto ii) DCTS_LAMBDA_INLINE {
-      constexpr int i = decltype(ii)::value;
-      f2_load_item<M, L, W + NW * i, 0>(rs, vo, pre[i]);
-    });
-  }
+  static_assert(P1::ITEMS <= ROUNDS, "one item of the next map per pass-2 round");
+  typename P1::Pre pre;
+  if (m < nmaps) DCTS_F2_FIRST_STRIP(W, NW, tile_in(tb, m), lane_in, pre)
   for (; m < nmaps; m += gridDim.x) {
     const float* in_b = tile_in(tb, m, &hint_in);
     float parked[2][STRIPS][M];
@@ -98,17 +75,7 @@ __device__ __forceinline__ void fused2_body(const TileBatch& tb, lds_ptr buf0, l
       int lane = launder(lane_in);
       const bool act = s * SW + lane < N;
       DCTS_STAMP(2);
-      {
-        const __amdgpu_buffer_rsrc_t rs = map_rsrc(in_b, true);
-        const int vo = (s + 1 < STRIPS) ? lane_voff(s + 1) : 0;
-        dcts::static_for<ITEMS>([&](auto ii) DCTS_LAMBDA_INLINE {
-          constexpr int i = decltype(ii)::value;
-          f2_network_store<M, L, W + NW * i>(pre[i], buf, SW, lane, act);
-          // the registers of this item are free: request its samples of the next strip
-          if constexpr (s + 1 < STRIPS) f2_load_item<M, L, W + NW * i, (s + 1 < STRIPS ? s + 1 : 0)>(rs, vo, pre[i]);
-          __builtin_amdgcn_sched_barrier(0);
-        });
-      }
+      DCTS_F2_STRIP(W, NW, s, in_b, buf, lane_in, lane, act, pre)
       DCTS_STAMP(3);
       lds_barrier();  // the image of strip s is complete; everyone is past the codelets of strip s - 1 (the other buffer)
       DCTS_STAMP(4);
@@ -148,25 +115,10 @@ __device__ __forceinline__ void fused2_body(const TileBatch& tb, lds_ptr buf0, l
       int lane = launder(lane_in);
       dcts::static_for<2>([&](auto ii) DCTS_LAMBDA_INLINE {
         constexpr int i = decltype(ii)::value;
-        dcts::static_for<STRIPS>([&](auto is) DCTS_LAMBDA_INLINE {
-          constexpr int s = decltype(is)::value;
-          const int line = s * SW + lane;
-          const int off = (line < N ? line : 0) * RW + (2 * W + i) * KPR;
-          dcts::static_for<KPR>([&](auto ic) DCTS_LAMBDA_INLINE {
-            constexpr int c = decltype(ic)::value;
-            if constexpr (r * KPR + c < M) {
-              if (line < N) blk[off + c] = parked[i][s][r * KPR + c];
-            } else {
-              if (line < N) blk[off + c] = 0.f;  // padding column: contributes exactly zero energy
-            }
-          });
-        });
+        DCTS_DUMP_BALANCED(2 * W + i, STRIPS, r, blk, lane, parked[i][s][k])
       });
       DCTS_STAMP(7);
-      if constexpr (r < ITEMS) {  // round r's dump has freed registers: item r of the next map's first strip
-        const __amdgpu_buffer_rsrc_t rs = map_rsrc(next_b, more_maps);
-        f2_load_item<M, L, W + NW * (r < ITEMS ? r : 0), 0>(rs, lane_voff(0), pre[r < ITEMS ? r : 0]);
-      }
+      DCTS_F2_NEXT_MAP_ITEM(W, NW, r, next_b, more_maps, lane_in, pre)
       lds_barrier();
       DCTS_STAMP(8);
       lane = launder(lane_in);
@@ -178,9 +130,10 @@ __device__ __forceinline__ void fused2_body(const TileBatch& tb, lds_ptr buf0, l
       dcts::static_for<2>([&](auto ii) DCTS_LAMBDA_INLINE {
         constexpr int i = decltype(ii)::value;
         const int ln = launder(lane_in);
+        // DCTS_ROUND_TAIL written out: its row test (act && iH >= 0) moved the listing of k_split_fused2_coeff
         float o[M];
         split_role_transform<M, L, 2 * W + i>(blk + (ln < COLS ? ln : 0), RW, o);
-        if constexpr (STORE) {  // see fused_body
+        if constexpr (STORE) {  // balanced_leaf_row()
           const int q = ln / KPR, kh = r * KPR + (ln - q * KPR);
           if (ln < COLS && kh < M) {
             float* dst = leaf_out + ((long long)m * N + q * M + kh) * N + (2 * W + i) * M;
@@ -219,10 +172,7 @@ __device__ __forceinline__ void fused2_body(const TileBatch& tb, lds_ptr buf0, l
     lds_barrier();
     finish(partials, pending_slot, pending_m);
   }
-#ifdef DCTS_FUSED_STAMPS
-  if (lane_in == 0)
-    for (int i = 0; i < 16; ++i) atomicAdd(&g_fused_stamps[W][i], acc_[i]);
-#endif
+  DCTS_STAMP_END(W, lane_in);
 }
 
 template <int M, int L, bool STORE, int... Wv>
@@ -259,43 +209,21 @@ int launch_fused2(const TileBatch& tb, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-template <int M, int L>
-int coeff_fused2(const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps, hipStream_t st) {
-  auto launch = [st](const TileBatch& tb, float* leaf) {
-    const long long grid = tb.total < num_cus() ? tb.total : num_cus();
-    hipLaunchKernelGGL((k_split_fused2_coeff<M, L>), dim3((unsigned)grid), dim3(64 * Fused2Cfg<M, L>::NW), 0, st, tb, leaf);
-    return (int)hipGetLastError();
-  };
-  return run_coeff_chunks(launch, launch_assemble<M, L, true>, M << L, x, nmaps, out, scratch, scratch_maps, st);
-}
-
 }  // namespace
 
 namespace dctsi {
 
 int dispatch_fused2_coeff(int N, const float* x, long long nmaps, float* out, float* scratch, long long scratch_maps,
                           hipStream_t st) {
-#define DCTS_CASE(N_, M_, L_) \
-  case N_:                    \
-    return coeff_fused2<M_, L_>(x, nmaps, out, scratch, scratch_maps, st);
-  switch (N) {
-    DCTS_FUSED2_TABLE(DCTS_CASE)
-    default:
-      return DCTS_E_UNSUPPORTED;
-  }
-#undef DCTS_CASE
+  DCTS_SWITCH_TABLE(DCTS_FUSED2_TABLE, N, [&](auto m, auto l) {
+    constexpr int M = decltype(m)::value, L = decltype(l)::value;
+    return coeff_role_waves<M, L, k_split_fused2_coeff<M, L>, Fused2Cfg<M, L>::NW>(x, nmaps, out, scratch, scratch_maps, st);
+  })
 }
 
 int dispatch_fused2(int N, const TileBatch& tb, hipStream_t st) {
-#define DCTS_CASE(N_, M_, L_) \
-  case N_:                    \
-    return launch_fused2<M_, L_>(tb, st);
-  switch (N) {
-    DCTS_FUSED2_TABLE(DCTS_CASE)
-    default:
-      return DCTS_E_UNSUPPORTED;
-  }
-#undef DCTS_CASE
+  DCTS_SWITCH_TABLE(DCTS_FUSED2_TABLE, N,
+                    [&](auto m, auto l) { return launch_fused2<decltype(m)::value, decltype(l)::value>(tb, st); })
 }
 
 }  // namespace dctsi

@@ -13,7 +13,7 @@ namespace {
 // ---------------------------------------------------------------------------------------
 // pipelined fused kernel: pass 2 of map m interleaved with pass 1 of map m+1
 // ---------------------------------------------------------------------------------------
-// The fused kernel above streams a map in (pass 1, HBM-bound), then transforms the parked tile
+// The fused kernel (fused.hip) streams a map in (pass 1, HBM-bound), then transforms the parked tile
 // (pass 2, no HBM traffic at all): the two halves alternate and neither the memory system nor the
 // VALUs are ever busy for more than half of the time. Here one step = pass-2 round r of the
 // previous map followed by pass-1 strip r of the current one, so the direct-to-LDS loads of strip
@@ -99,10 +99,7 @@ __device__ __forceinline__ void pipe_body(const PlainMaps& tb, lds_ptr buf0, lds
   const lds_ptr park = parkbuf + (ROLE * 64 + lane_in);  // [T * NP][64 * S]
   long long m_cur = blockIdx.x, m_prev = -1, pending_m = -1;
   int pslot = 0, pending_slot = 0;
-#ifdef DCTS_FUSED_STAMPS
-  unsigned long long acc_[16] = {}, last_;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(last_)::"memory");
-#endif
+  DCTS_STAMP_BEGIN();
   const long long nmaps = tb.total;
   if (m_cur < nmaps) {
     const float* first = tile_in(tb, m_cur);
@@ -144,12 +141,13 @@ __device__ __forceinline__ void pipe_body(const PlainMaps& tb, lds_ptr buf0, lds
         DCTS_STAMP(0);
         if constexpr (r == 0) {
           if (pending_m >= 0) {
-            fused_finish<M, L, ROLE>(partials, pending_slot, pending_m, tb, lane_in);
+            fused_finish<M, L, S, ROLE>(partials, pending_slot, pending_m, tb, lane_in);
             pending_m = -1;
           }
         }
         if constexpr (have_cur) issue(in_b, r, dat, Q2{});
         int lane = launder(lane_in);
+        // DCTS_DUMP_BALANCED written out: a value from the LDS park is read before the line test, not under it
         dcts::static_for<T>([&](auto is) DCTS_LAMBDA_INLINE {
           constexpr int s = decltype(is)::value;
           const int line = s * SW + lane;
@@ -179,13 +177,7 @@ __device__ __forceinline__ void pipe_body(const PlainMaps& tb, lds_ptr buf0, lds
         lds_barrier();
         DCTS_STAMP(4);
         lane = launder(lane_in);
-        float o[M];
-        split_role_transform<M, L, ROLE>(img + lane, RW, o);
-        float er = 0.f;
-        dcts::static_for<M>([&](auto ik) DCTS_LAMBDA_INLINE {
-          constexpr int kk = decltype(ik)::value;
-          er = fmaf(o[kk], o[kk], er);
-        });
+        DCTS_ROUND_TAIL(ROLE, false, img + lane, RW, true, 0, (float*)nullptr, 0, o, er)  // no coefficient instantiation
         asm volatile("" : "+v"(er));
         e += er;
         DCTS_STAMP(5);
@@ -263,12 +255,9 @@ __device__ __forceinline__ void pipe_body(const PlainMaps& tb, lds_ptr buf0, lds
   }
   if (pending_m >= 0) {
     lds_barrier();
-    fused_finish<M, L, ROLE>(partials, pending_slot, pending_m, tb, lane_in);
+    fused_finish<M, L, S, ROLE>(partials, pending_slot, pending_m, tb, lane_in);
   }
-#ifdef DCTS_FUSED_STAMPS
-  if (lane_in == 0)
-    for (int i = 0; i < 16; ++i) atomicAdd(&g_fused_stamps[ROLE][i], acc_[i]);
-#endif
+  DCTS_STAMP_END(ROLE, lane_in);
 }
 
 template <int M, int L, int... R>
@@ -292,13 +281,7 @@ __global__ __launch_bounds__((64 << L), (fused_waves_per_simd<M, L>())) void k_s
 
 template <int M, int L>
 int launch_pipe(const TileBatch& tb, hipStream_t st) {  // one tensor per launch (PlainMaps)
-  static const int per_cu = [] {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_split_pipe<M, L>, 64 << L, 0) != hipSuccess || n < 1)
-      n = 1;
-    return n;
-  }();
-  const long long cap = (long long)num_cus() * per_cu;
+  const long long cap = (long long)num_cus() * blocks_per_cu<k_split_pipe<M, L>, (1 << L)>();
   int rc = 0;
   for (int i = 0; i < tb.count && !rc; ++i) {
     const long long nm = tb.begin[i + 1] - tb.begin[i];
@@ -315,15 +298,8 @@ int launch_pipe(const TileBatch& tb, hipStream_t st) {  // one tensor per launch
 namespace dctsi {
 
 int dispatch_pipe(int N, const TileBatch& tb, hipStream_t st) {
-#define DCTS_CASE(N_, M_, L_) \
-  case N_:                    \
-    return launch_pipe<M_, L_>(tb, st);
-  switch (N) {
-    DCTS_PIPE_TABLE(DCTS_CASE)
-    default:
-      return DCTS_E_UNSUPPORTED;
-  }
-#undef DCTS_CASE
+  DCTS_SWITCH_TABLE(DCTS_PIPE_TABLE, N,
+                    [&](auto m, auto l) { return launch_pipe<decltype(m)::value, decltype(l)::value>(tb, st); })
 }
 
 }  // namespace dctsi
