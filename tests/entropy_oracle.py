@@ -36,8 +36,10 @@ from oracle import dct_oracle as orc  # noqa: E402
 R = 5.192e-6     # measured with the command above: "scale 2^20" sets it; 8 R = 4.154e-5
 TOL = 8 * R
 
-FUSED_EDGES = (2, 4, 7, 8, 9, 14, 16, 28, 32, 56, 64)
-PAD_EDGES = (7, 13)                       # 7 -> 8 and 13 -> 14 with pad_front_if_odd
+# every codelet edge and every odd edge the front pad takes to one: each (edge, pad) is an instantiation of k_entropy_codelet
+# of its own (tests/test_entropy_gpu.py and tests/test_entropy_cpu.py assert that these are the library's lists)
+FUSED_EDGES = (2, 4, 6, 7, 8, 9, 10, 12, 14, 16, 18, 20, 24, 28, 30, 32, 36, 40, 48, 56, 60, 64)
+PAD_EDGES = (1, 3, 5, 7, 9, 11, 13, 15, 17, 19, 23, 27, 29, 31, 35, 39, 47, 55, 59, 63)  # h -> h + 1 with pad_front_if_odd
 BASIS_EDGES = (8, 14)
 FALLBACK_SHAPES = ((56, 28), (13, 13), (72, 72), (288, 288))
 PITCH_EDGE, PITCH = 16, 20
@@ -88,13 +90,24 @@ def _basis32(n, ortho):
     return b.astype(np.float32)
 
 
-def entropy_nc_f32(x, c_begin=0, c_count=None, pad_front_if_odd=False, scale="kernel"):
-    """Every step in float32 (numpy float32 [N, c_count]); scale: "kernel" (unnormalised) or "ortho"."""
+def coefficients_f32(x, c_begin=0, c_count=None, pad_front_if_odd=False, scale="kernel"):
+    """The restatement's coefficients, numpy float32 [N, c_count, H', W']: a float32 matrix product per axis."""
     a = _slice(x, c_begin, c_count, pad_front_if_odd, np.float32)
-    hp, wp = a.shape[2], a.shape[3]
-    bh, bw = _basis32(hp, scale == "ortho"), _basis32(wp, scale == "ortho")
+    bh, bw = _basis32(a.shape[2], scale == "ortho"), _basis32(a.shape[3], scale == "ortho")
     w = np.matmul(np.matmul(bh, a), bw.T)
     assert w.dtype == np.float32
+    return w
+
+
+def entropy_nc_f32(x, c_begin=0, c_count=None, pad_front_if_odd=False, scale="kernel"):
+    """Every step in float32 (numpy float32 [N, c_count]); scale: "kernel" (unnormalised) or "ortho"."""
+    return entropy_of_coefficients_f32(coefficients_f32(x, c_begin, c_count, pad_front_if_odd, scale))
+
+
+def entropy_of_coefficients_f32(w):
+    """The one-pass formula on float32 coefficients [..., H', W'] of any common scale -> float32 [...]."""
+    assert w.dtype == np.float32
+    hp, wp = w.shape[-2], w.shape[-1]
     sq = w * w
     e = sq.sum(axis=(-2, -1), dtype=np.float32)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -141,6 +154,30 @@ def pair_maps(n):
     return torch.from_numpy(np.stack(maps)[None].astype(np.float32))
 
 
+def unequal_pair_maps(n):
+    """[1, n * n, n, n]: map u * n + v is basis(p) + 0.5 * basis(u, v), built in float64 and rounded once; the partner p is
+    (1 % n, 2 % n), or (2 % n, 1 % n) where that is (u, v) itself. p = (0.8, 0.2): H = -(0.8 ln 0.8 + 0.2 ln 0.2) = 0.5004,
+    and where the equal pairs sit at the maximum of H (a relative error eps in one weight moves ln 2 by eps^2 / 2), here it
+    moves H by 0.44 eps: every coefficient's weight is seen, the 1 / sqrt(2) of the DC row and column included."""
+    b = _basis64(n)
+    u, v = np.divmod(np.arange(n * n), n)
+    first = (u == 1 % n) & (v == 2 % n)
+    pu, pv = np.where(first, 2 % n, 1 % n), np.where(first, 1 % n, 2 % n)
+    assert not ((pu == u) & (pv == v)).any()
+    maps = b[pu][:, :, None] * b[pv][:, None, :] + 0.5 * (b[u][:, :, None] * b[v][:, None, :])
+    return torch.from_numpy(maps[None].astype(np.float32))
+
+
+def padded_unequal_pair_maps(edge):
+    """[1, (edge + 1)^2, edge, edge] for an odd edge: the unequal pairs of the padded tile without their first row and
+    column. The front pad puts zeros there, so no such map is a pair any more; the float64 definition, which pads the same
+    way, is the yardstick."""
+    return unequal_pair_maps(edge + 1)[:, :, 1:, 1:].contiguous()
+
+
+H_UNEQUAL = -(0.8 * math.log(0.8) + 0.2 * math.log(0.2))
+
+
 def _basis64(n):
     k = np.arange(n, dtype=np.float64)
     b = np.cos(np.pi * (2 * k[None, :] + 1) * k[:, None] / (2 * n)) * math.sqrt(2.0 / n)
@@ -182,6 +219,10 @@ def gpu_inputs():
     for e in BASIS_EDGES:
         yield "basis %d" % e, basis_maps(e), False, ("kernel",)
         yield "pairs %d" % e, pair_maps(e), False, ("kernel",)
+    for e in FUSED_EDGES:
+        yield "unequal %d" % e, unequal_pair_maps(e), False, ("kernel",)
+    for e in PAD_EDGES:
+        yield "pad unequal %d" % e, padded_unequal_pair_maps(e), True, ("kernel",)
     for name, x in zip(("scale 1", "scale 2^20", "scale 2^-20"), scale_case()):
         yield name, x, False, ("kernel",)
     for h, w in FALLBACK_SHAPES:

@@ -132,6 +132,80 @@ def metric_bound(x, K, metric, terms):
     return distance_bound(x, K, terms) / float(live.min()) if live.size else 0.0
 
 
+# ----------------------------------------------------------------------------------------------------
+# the cases of the per-edge probes (tests/test_lowpass_gpu.py, tests/test_lowpass_probes_gpu.py, tests/test_lowpass_cpu.py)
+# ----------------------------------------------------------------------------------------------------
+# Every edge with a codelet: each is an instantiation of k_lowpass_codelet of its own. The GPU and CPU files assert that this
+# is the library's list.
+CODELET_EDGES = (2, 4, 6, 7, 8, 9, 10, 12, 14, 16, 18, 20, 24, 28, 30, 32, 36, 40, 48, 56, 60, 64)
+FLAT_VALUES = (3.7, 0.0, -1.25)                  # what a flat map holds, in turn
+NOT_FLAT = ("random", "last", "first", "nan")    # what a map that is not flat is, in turn
+
+
+def group_size(n):
+    """G: the maps a wave of the codelet kernel holds at edge n."""
+    return 64 // n
+
+
+def corner_sizes(n):
+    """The K of a probe at edge n: small ones, both sides of a multiple of 4, the last two."""
+    return sorted({k for k in (1, 2, 3, 4, 5, 8, 12, n - 1, n) if 1 <= k <= n})
+
+
+def on_vector_chain(n, K, aligned=True):
+    """The kernel's own rule for the 16-byte store chain: several maps per wave, K a multiple of 4, a 16-byte-aligned out."""
+    return group_size(n) >= 2 and K % 4 == 0 and aligned
+
+
+def chain_sizes(n):
+    """(K on the 16-byte chain or None, K on the scalar chain) for the drop_dc probe at edge n. No K <= 2 is a multiple
+    of 4, so edge 2 has the scalar chain only."""
+    vec = 8 if n >= 8 else (4 if n >= 4 else None)
+    return (vec if group_size(n) >= 2 else None), (5 if n >= 5 else min(n, 3))
+
+
+def flat_pattern_count(n):
+    """Maps of a flat pattern: at least 2 G + 1 (two full groups and a ragged one), and enough that each parity holds all
+    four kinds of a map that is not flat."""
+    return max(2 * group_size(n) + 1, 9)
+
+
+def flat_pattern_maps(n, parity, seed=0):
+    """(x [1, C, n, n] float32, kinds): channel j is flat iff j % 2 == parity, with the values of FLAT_VALUES in turn; the
+    others take the kinds of NOT_FLAT in turn: a random map, 3.7 except for the last element, 3.7 except for the first
+    element, 3.7 except for one NaN. kinds[j] is "flat" or the kind."""
+    C = flat_pattern_count(n)
+    x = torch.randn(1, C, n, n, generator=torch.Generator().manual_seed(8000 + 10 * n + seed))
+    kinds, nf, fl = [], 0, 0
+    for j in range(C):
+        if j % 2 == parity:
+            x[0, j] = FLAT_VALUES[fl % len(FLAT_VALUES)]
+            fl += 1
+            kinds.append("flat")
+            continue
+        kind = NOT_FLAT[nf % len(NOT_FLAT)]
+        nf += 1
+        kinds.append(kind)
+        if kind == "random":
+            continue
+        x[0, j] = 3.7
+        if kind == "last":
+            x[0, j, n - 1, n - 1] = 3.7000003
+        elif kind == "first":
+            x[0, j, 0, 0] = 0.0
+        else:
+            x[0, j, n // 2, 0] = float("nan")
+    return x, kinds
+
+
+def basis_bank(n):
+    """[1, n * n, n, n] float64: map u * n + v is basis_map(n, u, v)."""
+    k = np.arange(n)
+    c = np.cos(np.pi * (2 * k[None, :] + 1) * k[:, None] / (2 * n)) * np.sqrt(2.0 / n)
+    c[0] = np.sqrt(1.0 / n)
+    return np.einsum("ui,vj->uvij", c, c).reshape(1, n * n, n, n)
+
+
 def basis_map(n, u, v):
     """The n x n map whose orthonormal DCT is 1 at [u, v] and 0 elsewhere: outer(C[u, :], C[v, :])."""
     k = np.arange(n)

@@ -91,14 +91,24 @@ def test_placement_fallback_on_a_codelet_shape(edge):
     _placement(edge, edge, "square", 4, dpa.ALGO_DIRECT, "fallback")
 
 
-@pytest.mark.parametrize("edge", [7, 9])
-@pytest.mark.parametrize("algo", [dpa.ALGO_CODELET, dpa.ALGO_DIRECT])
+PAD_EDGES = [h for h in range(1, 64, 2) if h + 1 in CODELET_EDGES]  # the odd edges the front pad takes to a codelet
+PAD_CASES = [(dpa.ALGO_CODELET, h) for h in PAD_EDGES] + [(dpa.ALGO_DIRECT, 7), (dpa.ALGO_DIRECT, 9)]
+
+
+def test_padded_edge_list_is_the_librarys():
+    assert PAD_EDGES == [1, 3, 5, 7, 9, 11, 13, 15, 17, 19, 23, 27, 29, 31, 35, 39, 47, 55, 59, 63]
+    assert PAD_EDGES == [h for h in range(1, 64, 2) if dpa.has_codelet(h + 1, h + 1)]
+
+
+@pytest.mark.parametrize("algo,edge", PAD_CASES, ids=["%d-%d" % c for c in PAD_CASES])
 def test_placement_with_the_odd_pad(edge, algo):
     """A basis function of the padded (edge + 1)^2 tile is not zero in its first row and column, so a padded map cannot
     be a single basis function: the maps are the basis functions of the padded tile with that row and column cut off,
-    and every band is compared with the float64 definition (which pads the same way) instead of with 0 / 1."""
+    and every band is compared with the float64 definition (which pads the same way) instead of with 0 / 1. Every padded
+    edge is a kernel of its own (the load with its zero fill, the group size and the slab strides of edge + 1)."""
     p = edge + 1
-    pairs = dp.cover(p, p, exhaustive=True)
+    assert dpa.has_band_kernel(p, p)
+    pairs = _pairs(p, p)  # all u x all v up to a padded edge of 32, as the unpadded placement test
     x = dp.basis_maps(p, p, pairs)[None, :, 1:, 1:].contiguous()
     for kind in ("square", "diag"):
         for K in (2, 4, 8):

@@ -105,6 +105,81 @@ def test_oracle_two_equal_basis_functions_give_ln2(n):
     np.testing.assert_allclose(eo.entropy_nc_f32(eo.pair_maps(n)), math.log(2.0), rtol=0, atol=eo.TOL)
 
 
+def test_probe_edge_lists_are_the_librarys():
+    lib = _lib.load()
+    edges = [e for e in range(1, 65) if lib.dcts_has_codelet(e, e)]
+    assert edges == list(eo.FUSED_EDGES) and len(edges) == 22
+    assert [h for h in range(1, 64, 2) if lib.dcts_has_codelet(h + 1, h + 1)] == list(eo.PAD_EDGES) and len(eo.PAD_EDGES) == 20
+    assert all(lib.dcts_has_entropy_kernel(e, e) == 1 for e in edges)
+    names = [name for name, _, _, _ in eo.gpu_inputs()]
+    for e in eo.FUSED_EDGES:
+        assert "fused %d" % e in names and "unequal %d" % e in names
+    for e in eo.PAD_EDGES:
+        assert "pad %d" % e in names and "pad unequal %d" % e in names
+
+
+@pytest.mark.parametrize("n", [2, 7, 8, 14, 20])
+def test_oracle_unequal_pairs(n):
+    x = eo.unequal_pair_maps(n)
+    assert tuple(x.shape) == (1, n * n, n, n) and x.dtype == torch.float32
+    # the construction: coefficient p is 1 and (u, v) is 1 / 2, everything else 0
+    c = orc.dct_2d_f64(x.numpy().astype(np.float64))[0]
+    for m in range(n * n):
+        u, v = divmod(m, n)
+        p = (1 % n, 2 % n) if (u, v) != (1 % n, 2 % n) else (2 % n, 1 % n)
+        want = np.zeros((n, n))
+        want[p] = 1.0
+        want[u, v] = 0.5
+        np.testing.assert_allclose(c[m], want, atol=1e-6)
+    assert eo.H_UNEQUAL == pytest.approx(0.5004024, abs=1e-7)
+    np.testing.assert_allclose(eo.entropy_nc_f64(x), eo.H_UNEQUAL, rtol=0, atol=1e-6)
+    np.testing.assert_allclose(eo.entropy_nc_f32(x), eo.H_UNEQUAL, rtol=0, atol=eo.TOL)
+    if n % 2 == 0:  # under the pad: the padded tile's pairs without the row and column the pad gives back as zeros
+        y = eo.padded_unequal_pair_maps(n - 1)
+        assert tuple(y.shape) == (1, n * n, n - 1, n - 1)
+        np.testing.assert_array_equal(y.numpy(), x.numpy()[:, :, 1:, 1:])
+        ref = eo.entropy_nc_f64(y, pad_front_if_odd=True)
+        np.testing.assert_array_equal(ref, eo.entropy_nc_f64(torch.nn.functional.pad(y, (1, 0, 1, 0))))
+        assert np.abs(eo.entropy_nc_f32(y, pad_front_if_odd=True).astype(np.float64) - ref).max() <= eo.TOL
+
+
+@pytest.mark.parametrize("n", eo.BASIS_EDGES)
+@pytest.mark.parametrize("where", ["dc-row", "interior"])
+def test_unequal_pairs_catch_one_wrong_weight_that_the_equal_pairs_miss(n, where):
+    """What the unequal pairs are for. The mutant is the fp32 restatement with the weight of ONE coefficient off by 1e-3
+    (a wrong 1 / sqrt(2) of the DC row, a wrong entry of a twiddle table). At p = (1/2, 1/2), the maximum of H, that moves
+    ln 2 by eps^2 / 2 = 5e-7; a single basis function has H = 0 whatever its weight. Both old probes pass the mutant at
+    TOL = 4.2e-5. At p = (0.8, 0.2) it moves H by 0.44 eps = 4.4e-4, ten times TOL."""
+    u, v = (0, 1) if where == "dc-row" else (2, 3)
+    eps = 1e-3
+
+    def mutant(x):
+        w = eo.coefficients_f32(x).copy()
+        w[..., u, v] *= np.float32(1.0 + eps)
+        return eo.entropy_of_coefficients_f32(w).astype(np.float64)
+
+    def honest(x):
+        return eo.entropy_nc_f32(x).astype(np.float64)
+
+    pairs, basis, unequal = eo.pair_maps(n), eo.basis_maps(n), eo.unequal_pair_maps(n)
+    # the mutated coefficient is one of an equal pair (tests/entropy_oracle.py: (0, 1) + (n-1, n-1) and (2, 3) + (3, 2))
+    c = orc.dct_2d_f64(pairs.numpy().astype(np.float64))[0]
+    assert (np.abs(c[:, u, v]) > 0.9).any()
+    err_pairs = np.abs(mutant(pairs) - math.log(2.0)).max()
+    err_basis = np.abs(mutant(basis)).max()
+    ref = eo.entropy_nc_f64(unequal)
+    err_unequal = np.abs(mutant(unequal) - ref)
+    err_honest = np.abs(honest(unequal) - ref).max()
+    print("ENTROPY mutant %d (%d, %d) * (1 + %.0e): pairs %.3e, basis %.3e, unequal pairs %.3e (honest %.3e), tol %.3e"
+          % (n, u, v, eps, err_pairs, err_basis, err_unequal.max(), err_honest, eo.TOL))
+    assert err_pairs <= eo.TOL and err_basis <= eo.TOL          # the old probes: blind to it
+    assert err_honest <= eo.R                                    # the restatement itself meets the new one
+    assert err_unequal.max() > 4 * eo.TOL                        # the new probe: far outside
+    # and it is the map whose half-amplitude partner is (u, v) that shows it, by 0.44 eps
+    assert int(err_unequal.argmax()) == u * n + v
+    assert err_unequal.max() == pytest.approx(0.4436 * eps, rel=0.05)
+
+
 def test_oracle_scale_invariance_bounds_and_pad():
     x, big, small = eo.scale_case()
     ref = eo.entropy_nc_f64(x)

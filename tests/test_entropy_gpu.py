@@ -1,6 +1,7 @@
 """dcts_spectral_entropy_f32 on the GPU against the float64 definition of tests/entropy_oracle.py, at the absolute tolerance
-derived there (TOL = 8 R, R the fp32 restatement's own error on these inputs): the fused kernel on every edge the nets
-hook, the odd pad, known answers, dead and poisoned maps, the fallback with its chunking, both grid-stride loops with
+derived there (TOL = 8 R, R the fp32 restatement's own error on these inputs): the fused kernel on every codelet edge and,
+with the odd pad, on every odd edge below one (each an instantiation of its own), known answers and the unequal pairs that
+see the weight of every single coefficient, dead and poisoned maps, the fallback with its chunking, both grid-stride loops with
 more maps than a grid holds, and the harness modes."""
 import math
 import time
@@ -43,6 +44,15 @@ def _check(got, x, pad=False, c_begin=0, c_count=None, what=""):
 # ----------------------------------------------------------------------------------------------------
 # fused route
 # ----------------------------------------------------------------------------------------------------
+def test_edge_lists_are_the_librarys():
+    """Every codelet edge is an instantiation k_entropy_codelet<N, 0>, every odd edge below one a k_entropy_codelet<N, 1>."""
+    edges = [e for e in range(1, 65) if dpa.has_codelet(e, e)]
+    assert edges == list(eo.FUSED_EDGES) and len(edges) == 22 and all(dpa.has_entropy_kernel(e, e) for e in edges)
+    odd = [h for h in range(1, 64, 2) if dpa.has_codelet(h + 1, h + 1)]
+    assert odd == list(eo.PAD_EDGES) and len(odd) == 20
+    assert set(eo.BASIS_EDGES) <= set(eo.FUSED_EDGES)
+
+
 @pytest.mark.parametrize("edge", eo.FUSED_EDGES)
 def test_fused_kernel(edge):
     x = eo.fused_case(edge)
@@ -80,8 +90,10 @@ def test_fused_kernel_on_a_channel_slice_of_a_sample_strided_view(edge):
 @pytest.mark.parametrize("edge", eo.PAD_EDGES)
 def test_odd_pad(edge):
     x = eo.pad_case(edge)
+    assert dpa.has_entropy_kernel(edge + 1, edge + 1)
     got = dpa.spectral_entropy_nc(x.to(DEV), pad_front_if_odd=True)
     _check(got, x, pad=True, what="pad %d -> %d" % (edge, edge + 1))
+    assert torch.equal(_bits(got), _bits(dpa.spectral_entropy_nc(x.to(DEV), pad_front_if_odd=True, algo=dpa.ALGO_CODELET)))
     padded = torch.nn.functional.pad(x, (1, 0, 1, 0)).to(DEV)
     np.testing.assert_allclose(dpa.spectral_entropy_nc(padded).cpu().numpy(), got.cpu().numpy(), rtol=0, atol=TOL)
     sl = dpa.spectral_entropy_nc(x.to(DEV), c_begin=2, c_count=3, pad_front_if_odd=True)
@@ -101,6 +113,36 @@ def test_basis_functions_and_pairs(n):
     assert (np.abs(pairs - LN2) <= TOL).all()
 
 
+def _report_unequal(what, got, ref):
+    dev = np.abs(got.cpu().numpy().astype(np.float64) - eo.H_UNEQUAL)
+    print("ENTROPY %s maps=%d H_f64 in [%.6f, %.6f], worst |got - %.4f| = %.3e"
+          % (what, ref.size, ref.min(), ref.max(), eo.H_UNEQUAL, dev.max()))
+
+
+@pytest.mark.parametrize("n", eo.FUSED_EDGES)
+def test_unequal_pairs(n):
+    """basis(p) + 0.5 * basis(u, v) for every (u, v) of the tile: p = (0.8, 0.2), where a relative error eps in the weight of
+    one coefficient moves H by 0.44 eps (the equal pairs sit at the maximum of H and move by eps^2 / 2:
+    tests/test_entropy_cpu.py holds the mutant that passes them and fails here)."""
+    x = eo.unequal_pair_maps(n)
+    assert tuple(x.shape) == (1, n * n, n, n)
+    got = dpa.spectral_entropy_nc(x.to(DEV), algo=dpa.ALGO_CODELET)
+    ref = _check(got, x, what="unequal pairs %d" % n)
+    assert np.abs(ref - eo.H_UNEQUAL).max() <= 1e-6  # the construction: rounding the maps to fp32 moves H by 2e-8
+    _report_unequal("unequal pairs %d" % n, got, ref)
+
+
+@pytest.mark.parametrize("edge", eo.PAD_EDGES)
+def test_unequal_pairs_under_the_odd_pad(edge):
+    """The unequal pairs of the padded tile without their first row and column, which the pad fills with zeros: no map is a
+    pair any more, so every value is compared with the float64 definition, which pads the same way."""
+    x = eo.padded_unequal_pair_maps(edge)
+    assert tuple(x.shape) == (1, (edge + 1) ** 2, edge, edge) and dpa.has_entropy_kernel(edge + 1, edge + 1)
+    got = dpa.spectral_entropy_nc(x.to(DEV), pad_front_if_odd=True, algo=dpa.ALGO_CODELET)
+    ref = _check(got, x, pad=True, what="unequal pairs, pad %d -> %d" % (edge, edge + 1))
+    _report_unequal("unequal pairs, pad %d -> %d" % (edge, edge + 1), got, ref)
+
+
 def test_scale_invariance():
     x, big, small = eo.scale_case()
     ref = _check(dpa.spectral_entropy_nc(x.to(DEV)), x, what="scale 1")
@@ -113,20 +155,28 @@ def test_scale_invariance():
 # ----------------------------------------------------------------------------------------------------
 # dead and poisoned maps
 # ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("edge,algo", [(8, dpa.ALGO_AUTO), (14, dpa.ALGO_AUTO), (56, dpa.ALGO_AUTO), (13, dpa.ALGO_AUTO), (16, dpa.ALGO_DIRECT)],
-                         ids=["8", "14", "56", "13-fallback", "16-direct"])
-def test_zero_maps_give_plus_zero_and_a_nan_map_stays_alone(edge, algo):
+@pytest.mark.parametrize("edge,algo,pad", [(8, dpa.ALGO_AUTO, False), (14, dpa.ALGO_AUTO, False), (56, dpa.ALGO_AUTO, False),
+                                           (13, dpa.ALGO_AUTO, False), (16, dpa.ALGO_DIRECT, False),
+                                           (10, dpa.ALGO_AUTO, False), (20, dpa.ALGO_AUTO, False),  # special strides, G = 6 and 3
+                                           (9, dpa.ALGO_AUTO, True)],                               # runs <10, 1>
+                         ids=["8", "14", "56", "13-fallback", "16-direct", "10", "20", "9-pad"])
+def test_zero_maps_give_plus_zero_and_a_nan_map_stays_alone(edge, algo, pad):
     x = eo.fused_case(edge if edge != 13 else 14)[..., :edge, :edge].contiguous()
     x[:, 2] = 0
     x[0, 4] = 0
     xd = x.to(DEV)
-    clean = dpa.spectral_entropy_nc(xd, algo=algo)
+    if pad:
+        assert dpa.has_entropy_kernel(edge + 1, edge + 1)
+        run = lambda t, algo: dpa.spectral_entropy_nc(t, pad_front_if_odd=True, algo=algo)
+    else:
+        run = lambda t, algo: dpa.spectral_entropy_nc(t, algo=algo)
+    clean = run(xd, algo)
     assert (_bits(clean[:, 2]) == 0).all() and int(_bits(clean[0, 4])) == 0  # +0.0: the sign bit too
     assert (clean[:, 0] > 0).all()
     for poison in (float("nan"), float("inf")):
         y = xd.clone()
         y[1, 3, edge // 2, 1] = poison
-        got = dpa.spectral_entropy_nc(y, algo=algo)
+        got = run(y, algo)
         assert bool(torch.isnan(got[1, 3])), poison
         keep = torch.ones_like(got, dtype=torch.bool)
         keep[1, 3] = False

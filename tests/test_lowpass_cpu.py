@@ -74,6 +74,86 @@ def test_oracle_drop_dc_and_flat_rule():
     assert (np.diagonal(d, axis1=1, axis2=2) == 0).all()
 
 
+def test_probe_edge_list_is_the_librarys():
+    lib = _lib.load()
+    assert [e for e in range(1, 65) if lib.dcts_has_codelet(e, e)] == list(lo.CODELET_EDGES) and len(lo.CODELET_EDGES) == 22
+    for n in lo.CODELET_EDGES:
+        sizes = lo.corner_sizes(n)
+        assert sizes[0] == 1 and sizes[-1] == n and all(1 <= k <= n for k in sizes) and (n == 2 or n - 1 in sizes)
+        # both store chains wherever a wave holds several maps, but at edge 2 (no K <= 2 is a multiple of 4)
+        assert any(lo.on_vector_chain(n, k) for k in sizes) == (lo.group_size(n) >= 2 and n >= 4), n
+        assert any(not lo.on_vector_chain(n, k) for k in sizes)
+        assert not any(lo.on_vector_chain(n, k, aligned=False) for k in sizes)
+        vec, scalar = lo.chain_sizes(n)
+        assert (vec is None) == (n == 2 or n > 32) and (vec is None or (vec <= n and lo.on_vector_chain(n, vec)))
+        assert 1 <= scalar <= n and not lo.on_vector_chain(n, scalar)
+
+
+@pytest.mark.parametrize("n", lo.CODELET_EDGES)
+def test_oracle_on_the_basis_sweep_gives_the_identity_corner(n):
+    """The probe of tests/test_lowpass_probes_gpu.py before it meets a kernel: on basis map (u, v) the definition has 1 at
+    [u][v] where u, v < K and 0 everywhere else, for every K the GPU files use, from float64 maps and from the fp32 maps the
+    kernels get (dct_probes.basis_maps: rounded once, so every coefficient is within a few 2^-24 of the ideal)."""
+    import dct_probes as dp
+    bank = lo.basis_bank(n)
+    for u, v in ((0, 0), (1, 3 % n), (n - 1, n - 1)):
+        np.testing.assert_array_equal(bank[0, u * n + v], lo.basis_map(n, u, v))
+    pairs = dp.cover(n, n, exhaustive=True)
+    assert pairs.tolist() == [[u, v] for u in range(n) for v in range(n)]  # map u * n + v is basis (u, v)
+    maps32 = dp.basis_maps(n, n, pairs)[None]
+    np.testing.assert_array_equal(maps32.numpy(), bank.astype(np.float32))
+    whole64, whole32 = lo.lowpass_f64(bank, n), lo.lowpass_f64(maps32, n)
+    eye = np.eye(n * n).reshape(1, n * n, n, n)
+    np.testing.assert_allclose(whole64, eye, atol=1e-13)
+    np.testing.assert_allclose(whole32, eye, atol=4 * 2.0 ** -24)
+    step = 1 if n <= 32 else (n * n // 512) | 1  # every K on at most ~600 of the maps: an odd stride visits every column
+    for K in lo.corner_sizes(n) + [n + 3]:
+        k = min(K, n)
+        s = lo.lowpass_f64(maps32[:, ::step], K)
+        assert s.shape == (1, len(range(0, n * n, step)), k, k)
+        np.testing.assert_array_equal(s, whole32[:, ::step, :k, :k])  # the definition's corner is a slice
+        np.testing.assert_allclose(s, eye[:, ::step, :k, :k], atol=4 * 2.0 ** -24)
+
+
+@pytest.mark.parametrize("n", [n for n in lo.CODELET_EDGES if lo.group_size(n) >= 2])
+def test_flat_patterns_classify_as_intended(n):
+    G = lo.group_size(n)
+    seen = {}
+    for parity in (0, 1):
+        x, kinds = lo.flat_pattern_maps(n, parity)
+        C = x.shape[1]
+        assert x.dtype == torch.float32 and tuple(x.shape) == (1, C, n, n) and C == lo.flat_pattern_count(n) >= 2 * G + 1 and C % 2 == 1
+        assert [k == "flat" for k in kinds] == [j % 2 == parity for j in range(C)]
+        assert lo.flat_maps(x).tolist() == [[k == "flat" for k in kinds]]
+        assert set(kinds) == {"flat"} | set(lo.NOT_FLAT)
+        flat_values = {float(x[0, j, 0, 0]) for j, k in enumerate(kinds) if k == "flat"}
+        assert flat_values == {float(np.float32(v)) for v in lo.FLAT_VALUES}
+        for j, k in enumerate(kinds):
+            m = x[0, j]
+            if k == "last":
+                assert (m.reshape(-1)[:-1] == np.float32(3.7)).all() and m[-1, -1] != np.float32(3.7) and abs(float(m[-1, -1]) - 3.7) < 1e-6
+            elif k == "first":
+                assert (m.reshape(-1)[1:] == np.float32(3.7)).all() and m[0, 0] == 0
+            elif k == "nan":
+                assert int(torch.isnan(m).sum()) == 1 and (m[~torch.isnan(m)] == np.float32(3.7)).all()
+            elif k == "random":
+                assert m.max() > m.min()
+        seen[parity] = [k == "flat" for k in kinds]
+        # the definition under drop_dc: flat maps all +0.0, a NaN map stays NaN
+        s = lo.lowpass_f64(x, min(n, 5), drop_dc=True)
+        for j, k in enumerate(kinds):
+            if k == "flat":
+                assert (s[0, j].view(np.int64) == 0).all()
+            elif k == "nan":
+                assert s[0, j, 0, 0] == 0 and np.isnan(s[0, j]).any()
+            else:
+                assert s[0, j, 0, 0] == 0 and np.abs(s[0, j]).max() > 0
+    # complementary: every position of a group of G maps holds a flat map in one pattern and a live one in the other
+    # (map j sits at position j % G of its group), and each map's neighbours in the wave are of the other kind
+    assert all(a != b for a, b in zip(seen[0], seen[1])) and len(seen[0]) > G
+    assert all(seen[0][j] != seen[0][j + 1] for j in range(len(seen[0]) - 1))
+
+
 def test_oracle_sees_what_the_option_is_for():
     a = torch.relu(torch.randn(1, 1, 14, 14, generator=torch.Generator().manual_seed(4))).double()
     b = a + torch.from_numpy(lo.basis_map(14, 5, 6))[None, None]

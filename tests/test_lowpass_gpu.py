@@ -1,6 +1,7 @@
 """dcts_dct2d_lowpass_f32 on the GPU against the float64 definition of tests/lowpass_oracle.py at 2e-6 of the batch's largest
 |coefficient| (the bound tests/test_gpu_coeff_large.py holds dct2d to): both routes, the orientation of the corner, the bits that
-must not depend on the call, drop_dc and the flat rule, the extent of what is written, the grid loop and far offsets."""
+must not depend on the call, drop_dc and the flat rule, the extent of what is written, the grid loop and far offsets.
+tests/test_lowpass_probes_gpu.py holds the per-coefficient probes of the fused route at every codelet edge."""
 import time
 
 import numpy as np
@@ -18,7 +19,7 @@ DEV = "cuda"
 TOL = lo.SIG_TOL    # of max |coefficient| of the batch
 BASIS_TOL = 5e-6    # a single basis function: one unit coefficient, everything else below this
 
-CODELET_EDGES = (2, 4, 7, 14, 20, 28, 56, 64)  # G = 32, 16, 9, 4, 3, 2, 1, 1: both special strides, idle lanes
+CODELET_EDGES = lo.CODELET_EDGES  # every instantiation of k_lowpass_codelet: G = 32 ... 1, the special strides, idle lanes
 FALLBACK = {  # name: (shape of the tensor the view is cut from, K)
     "13x17": ((2, 5, 13, 17), 8), "5x40": ((2, 5, 5, 40), 8), "33x33": ((1, 6, 33, 33), 8), "72x72": ((1, 5, 72, 72), 8),
     "pitched16": ((2, 5, 16, 20), 5),
@@ -53,20 +54,31 @@ def _fallback_view(name):
 # ----------------------------------------------------------------------------------------------------
 # the fused route
 # ----------------------------------------------------------------------------------------------------
+def test_codelet_edge_list_is_the_librarys():
+    assert [e for e in range(1, 65) if dpa.has_codelet(e, e)] == list(CODELET_EDGES) and len(CODELET_EDGES) == 22
+
+
 @pytest.mark.parametrize("n", CODELET_EDGES)
 def test_codelet_route_against_float64(n):
     G = 64 // n
     x = synth(1, 3 * G + 1, n, n, 500 + n, dead=True)  # the last group is ragged
     xd = x.to(DEV)
     assert dpa.has_codelet(n, n)
-    for K in sorted({k for k in (1, 2, 5, n) if k <= n}):
+    sizes = lo.corner_sizes(n)
+    # which store chain a K takes (the output of a call without out= is 16-byte aligned): where a wave holds several maps
+    # both chains run, but at edge 2, where no K <= n is a multiple of 4
+    vec = [K for K in sizes if G >= 2 and K % 4 == 0]
+    scalar = [K for K in sizes if not (G >= 2 and K % 4 == 0)]
+    assert scalar and (bool(vec) == (G >= 2 and n >= 4)), (n, G, vec, scalar)
+    assert vec == [K for K in sizes if lo.on_vector_chain(n, K)]
+    for K in sizes:
         got = dpa.lowpass_nc(xd, K)
-        assert got.shape == (1, 3 * G + 1, K, K)
-        _check(got, x, K, "codelet %d" % n)
-    if n == 7:  # K beyond the edge: the whole map, the same bits as K = n
-        big = dpa.lowpass_nc(xd, 12)
-        assert big.shape == (1, 3 * G + 1, 7, 7) and torch.equal(_bits(big), _bits(dpa.lowpass_nc(xd, 7)))
-        _check(big, x, 12, "codelet 7 clamp")
+        assert got.shape == (1, 3 * G + 1, K, K) and got.data_ptr() % 16 == 0
+        _check(got, x, K, "codelet %d (G = %d, %s chain)" % (n, G, "16-byte" if K in vec else "scalar"))
+    # K beyond the edge: the whole map, the same bits as K = n
+    big = dpa.lowpass_nc(xd, n + 3)
+    assert big.shape == (1, 3 * G + 1, n, n) and torch.equal(_bits(big), _bits(dpa.lowpass_nc(xd, n)))
+    _check(big, x, n + 3, "codelet %d clamp" % n)
 
 
 def test_codelet_channel_slice_of_a_sample_strided_view():
