@@ -17,7 +17,9 @@ Quirks kept because the result must equal the reference's state dict:
     stays as it was (:55-61);
   * ResNet-50: the downsample conv of a stage's first block does not update `last_select_index`
     (record_last = False, :506), batch-norm tensors follow the conv's kept filters, and every
-    `num_batches_tracked` is copied (:560).
+    `num_batches_tracked` is copied (:560); the downsample conv's INPUT channels are therefore selected by the
+    kept filters of the block's conv2, not of the block's input (downsample_input="block" selects by the latter:
+    not the reference, what prune.prune_network uses).
 
   * CIFAR ResNet-56/110: only `layerX.k.conv1/conv2` weights are transplanted (score files
     imp_conv2 ... - the counter starts at 1 and is incremented before use, :80, :89); a full-width conv
@@ -238,6 +240,15 @@ def _load_imp(imp_score, stem):
     return np.load(os.path.join(imp_score, stem + ".npy"))
 
 
+def _kept_rows(imp_score, stem, o, c):
+    """select_index on score file `stem`, which must hold one score per filter of its conv: with any other
+    length the argsort below would still return c indices, into the wrong filters or past the last one."""
+    imp = _load_imp(imp_score, stem)
+    if imp.shape != (o,):
+        raise ValueError("score file %s holds %s scores, its convolution has %d filters" % (stem, "x".join(map(str, imp.shape)), o))
+    return select_index(imp, o, c)
+
+
 def _rows(t, idx):
     return t.index_select(0, torch.as_tensor(idx, dtype=torch.long, device=t.device))
 
@@ -262,7 +273,7 @@ def transplant_vgg(state_dict, oristate_dict, imp_score, conv_names=None):
         ori, cur = oristate_dict[key], state_dict[key]
         o, c = ori.size(0), cur.size(0)
         if o != c:
-            sel = select_index(_load_imp(imp_score, "imp_conv%d" % cnt), o, c)
+            sel = _kept_rows(imp_score, "imp_conv%d" % cnt, o, c)
             if last is not None:
                 # [index_i][index_j] = ori[i][j] for i in select_index, j in last_select_index (:43-47);
                 # input channels beyond len(last) keep what the slim tensor had
@@ -278,28 +289,40 @@ def transplant_vgg(state_dict, oristate_dict, imp_score, conv_names=None):
     return state_dict
 
 
-def transplant_resnet_50(state_dict, oristate_dict, imp_score):
-    """utils/load_models.py:441-582 for args.net == 'resnet_50'."""
+def transplant_resnet_50(state_dict, oristate_dict, imp_score, downsample_input="conv2"):
+    """utils/load_models.py:441-582 for args.net == 'resnet_50'.
+
+    downsample_input: whose kept filters select the INPUT channels of a stage's downsample conv. "conv2", the default, is
+    the reference bit for bit: it uses last_select_index as it stands when the loop reaches the downsample conv, which
+    holds the kept filters of the block's conv2 (:525-529, :547-551), although that conv reads the block's input.
+    "block" uses the index the block was entered with (the kept filters of what feeds the block: the stem or the
+    previous stage's last conv3; None, the whole input, where that was not pruned), which is what the pruned module
+    computes with; prune.prune_network asks for it. Every other tensor is the same under both."""
+    if downsample_input not in ("conv2", "block"):
+        raise ValueError("downsample_input is 'conv2' or 'block', not %r" % (downsample_input,))
     honey = set()
-    last = None
-    for k, (conv, bn, record_last, _, _) in enumerate(resnet_50_convs()):
+    last = block_in = None
+    for k, (conv, bn, record_last, _, kind) in enumerate(resnet_50_convs()):
         key = conv + ".weight"
         honey.add(key)
         ori, cur = oristate_dict[key], state_dict[key]
         o, c = ori.size(0), cur.size(0)
         stem = k == 0
+        if conv.endswith(".0.conv1"):
+            block_in = last  # a stage's first block: what its conv1 and its downsample conv both read
+        cols = block_in if kind == "downsample" and downsample_input == "block" else last
         if o != c:
-            sel = select_index(_load_imp(imp_score, "imp_conv%d" % (k + 1)), o, c)
-            if last is not None and not stem:
-                cur[:, :len(last)] = _rows_cols(ori, sel, last)
+            sel = _kept_rows(imp_score, "imp_conv%d" % (k + 1), o, c)
+            if cols is not None and not stem:
+                cur[:, :len(cols)] = _rows_cols(ori, sel, cols)
             else:
                 cur.copy_(_rows(ori, sel))
             for part in _BN_PARTS:
                 state_dict[bn + part].copy_(_rows(oristate_dict[bn + part], sel))
             if record_last or stem:
                 last = sel
-        elif last is not None and not stem:
-            cur[:, :len(last)] = _rows_cols(ori, None, last)
+        elif cols is not None and not stem:
+            cur[:, :len(cols)] = _rows_cols(ori, None, cols)
             for part in _BN_PARTS:
                 state_dict[bn + part] = oristate_dict[bn + part]
             if record_last:
@@ -331,7 +354,7 @@ def transplant_resnet_cifar(state_dict, oristate_dict, imp_score, num_layers):
         ori, cur = oristate_dict[key], state_dict[key]
         o, c = ori.size(0), cur.size(0)
         if o != c:
-            sel = select_index(_load_imp(imp_score, stem), o, c)
+            sel = _kept_rows(imp_score, stem, o, c)
             if last is not None:
                 cur[:, :len(last)] = _rows_cols(ori, sel, last)
             else:
@@ -361,7 +384,7 @@ def transplant_densenet_40(state_dict, oristate_dict, imp_score, conv_names=None
         ori, cur = oristate_dict[key], state_dict[key]
         o, c = ori.size(0), cur.size(0)
         if o != c:
-            sel = [int(i) for i in select_index(_load_imp(imp_score, "imp_conv%d" % cov_id), o, c)]
+            sel = [int(i) for i in _kept_rows(imp_score, "imp_conv%d" % cov_id, o, c)]
             if last:
                 cur[:, :len(last)] = _rows_cols(ori, sel, last)
         else:
@@ -386,7 +409,7 @@ def transplant_googlenet(state_dict, oristate_dict, imp_score, filters=None, blo
     # pre_layers (cov_id 1, :332-358): transplanted only if it lost filters - the constructor never prunes it
     ori, cur = oristate_dict["pre_layers.0.weight"], state_dict["pre_layers.0.weight"]
     if ori.size(0) != cur.size(0):
-        sel = select_index(_load_imp(imp_score, "imp_conv1"), ori.size(0), cur.size(0))
+        sel = _kept_rows(imp_score, "imp_conv1", ori.size(0), cur.size(0))
         cur_last = [int(i) for i in sel]
         cur.copy_(_rows(ori, sel))
     for b, name in enumerate(blocks):
@@ -411,7 +434,7 @@ def transplant_googlenet(state_dict, oristate_dict, imp_score, filters=None, blo
             key = name + entry + ".weight"
             ori, cur = oristate_dict[key], state_dict[key]
             o, c = ori.size(0), cur.size(0)
-            sel = [int(i) for i in select_index(_load_imp(imp_score, "imp_conv%d%s" % (cov_id, stem)), o, c)] if o != c else list(range(o))
+            sel = [int(i) for i in _kept_rows(imp_score, "imp_conv%d%s" % (cov_id, stem), o, c)] if o != c else list(range(o))
             cur[:len(sel)] = _rows(ori, sel)
             if stem == "_n3x3":
                 cur_last += [x + f[0] for x in sel]
@@ -421,7 +444,7 @@ def transplant_googlenet(state_dict, oristate_dict, imp_score, filters=None, blo
         ori, cur = oristate_dict[key], state_dict[key]
         cols = sel5 if ori.size(1) != cur.size(1) else list(range(ori.size(1)))
         o, c = ori.size(0), cur.size(0)
-        sel = [int(i) for i in select_index(_load_imp(imp_score, "imp_conv%d_n5x5" % cov_id), o, c)] if o != c else list(range(o))
+        sel = [int(i) for i in _kept_rows(imp_score, "imp_conv%d_n5x5" % cov_id, o, c)] if o != c else list(range(o))
         cur_last += [x + f[0] + f[1] for x in sel]
         cur[:len(sel), :len(cols)] = _rows_cols(ori, sel, cols)
     # :361-380: every conv is on the sketch list (nothing to copy, biases included); batch-norms off the
@@ -519,8 +542,8 @@ def transplant_u2netp(state_dict, oristate_dict, imp_score, conv_names=None):
             saved_stage.append(list(last))
             saved = []
 
-        def rank():
-            return _load_imp(imp_score, "net.stage%d%s%s.relu_s1" % (stage_id, flag, midfix))
+        def kept():
+            return _kept_rows(imp_score, "net.stage%d%s%s.relu_s1" % (stage_id, flag, midfix), o, c)
 
         if not is_side:
             if decode and cov_id == "in":
@@ -530,7 +553,7 @@ def transplant_u2netp(state_dict, oristate_dict, imp_score, conv_names=None):
             else:
                 second = "unit"           # the RSU's own rebnconv<k> (:717)
             if o != c:
-                sel = select_index(rank(), o, c)
+                sel = kept()
                 rows = _rows(ori, sel)
                 if second is None:
                     if last is not None:
@@ -545,7 +568,7 @@ def transplant_u2netp(state_dict, oristate_dict, imp_score, conv_names=None):
                 if second != "unit":
                     saved.append(list(sel))
             elif last is not None:
-                sel = select_index(rank(), o, c)
+                sel = kept()
                 if second is not None:
                     other = saved[int(cov_id[0])]  # :658 reads cov_id[0] for 'in' too (ValueError there)
                 cols(cur, ori, last, 0, 0)
@@ -562,7 +585,7 @@ def transplant_u2netp(state_dict, oristate_dict, imp_score, conv_names=None):
         else:
             cnt += 1
             if o != c:
-                sel = select_index(_load_imp(imp_score, "net.side%d" % cnt), o, c)
+                sel = _kept_rows(imp_score, "net.side%d" % cnt, o, c)
                 rows = _rows(ori, sel)
                 if last is not None:
                     cols(cur, rows, last, 0, 0)

@@ -26,8 +26,6 @@ are sharded over the ranks and rank 0 writes the files.
 """
 import argparse
 import os
-from collections import OrderedDict
-
 import torch
 
 from dct_pruning_amd import bands, harness, nets
@@ -88,19 +86,7 @@ def parse_args(argv=None):
     return args
 
 
-def load_checkpoint(net, args):
-    """The five state-dict layouts of importance_generation.py:25-53."""
-    ckpt = torch.load(args.pretrain_dir, map_location="cpu", weights_only=True)
-    if args.net == "u2netp":
-        own = net.state_dict()
-        own.update({k: v for k, v in ckpt.items() if k in own})
-        net.load_state_dict(own)
-    elif args.net == "resnet_50":
-        net.load_state_dict(ckpt)
-    elif args.net in ("densenet_40", "resnet_110"):
-        net.load_state_dict(OrderedDict((k.replace("module.", ""), v) for k, v in ckpt["state_dict"].items()))
-    else:
-        net.load_state_dict(ckpt["state_dict"])
+load_checkpoint = nets.load_checkpoint  # python -m dct_pruning_amd.prune reads checkpoints the same way
 
 
 def main(argv=None):
