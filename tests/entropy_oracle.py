@@ -42,6 +42,7 @@ FUSED_EDGES = (2, 4, 6, 7, 8, 9, 10, 12, 14, 16, 18, 20, 24, 28, 30, 32, 36, 40,
 PAD_EDGES = (1, 3, 5, 7, 9, 11, 13, 15, 17, 19, 23, 27, 29, 31, 35, 39, 47, 55, 59, 63)  # h -> h + 1 with pad_front_if_odd
 BASIS_EDGES = (8, 14)
 FALLBACK_SHAPES = ((56, 28), (13, 13), (72, 72), (288, 288))
+DIRECT_SHAPES = ((100, 72), (260, 9))  # non-square with an edge beyond 64: the coefficients of the cosine-matrix kernel alone
 PITCH_EDGE, PITCH = 16, 20
 
 
@@ -195,6 +196,11 @@ def fallback_case(h, w):
     return mixed_maps(1, 3, h, w, 4000 + h + w)
 
 
+def direct_case(h, w):
+    """[2, 5, h, w]: two samples, so that a channel slice of it is not contiguous."""
+    return mixed_maps(2, 5, h, w, 4100 + h + w)
+
+
 def pitch_case(device="cpu"):
     """A [2, 5, 16, 16] view with strideH = 20 of a tensor on `device` whose pad columns hold 3.0. The tensor is moved
     first and sliced there: .to() of the view itself would hand back a dense copy."""
@@ -227,6 +233,8 @@ def gpu_inputs():
         yield name, x, False, ("kernel",)
     for h, w in FALLBACK_SHAPES:
         yield "fallback %dx%d" % (h, w), fallback_case(h, w), False, ("ortho",)
+    for h, w in DIRECT_SHAPES:
+        yield "direct %dx%d" % (h, w), direct_case(h, w), False, ("ortho",)
     yield "pitched 16", pitch_case().contiguous(), False, ("ortho",)
     yield "direct 16", fused_case(16), False, ("ortho",)
     b4, b5 = loop_banks()

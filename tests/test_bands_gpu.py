@@ -156,6 +156,24 @@ def test_accuracy_on_activations(H, W, pad):
                 assert err_alt <= tol
 
 
+@pytest.mark.parametrize("H,W", [(100, 72), (260, 9)])
+def test_accuracy_on_the_cosine_matrix_kernels_own_shapes(H, W):
+    """A non-square map with an edge beyond 64 (one of them beyond 256): every coefficient the band reduction reads is a dot
+    product of the cosine-matrix kernel. K = 4, channels 1 ... 3 of 5 in two samples: the slice is not contiguous."""
+    assert not dpa.has_band_kernel(H, W)
+    for signed in (False, True):
+        x = dp.random_maps(2, 5, H, W, seed=H + 7 * W + int(signed), signed=signed)
+        for kind in ("square", "diag"):
+            w = torch.from_numpy(bands.partition(H, W, 4, kind))
+            tol, e_ref = _tol(x[:, 1:4].contiguous(), w)
+            got = dpa.band_energy_nc(x.cuda(), w.cuda(), c_begin=1, c_count=3)
+            err = bo.band_error(got.cpu(), x, w, c_begin=1, c_count=3)
+            print("BANDS_ACC fallback %dx%d signed=%d %s4 channels 1..3 of 5 worst=%.3g E_ref=%.3g tol=%.3g" % (H, W, signed, kind, err, e_ref, tol))
+            assert err <= tol
+            full = dpa.band_energy_nc(x.cuda(), w.cuda())
+            assert torch.equal(got.view(torch.int32), full[:, 1:4].contiguous().view(torch.int32))
+
+
 # ---------------------------------------------------------------------------------------------------------
 # invariants
 # ---------------------------------------------------------------------------------------------------------

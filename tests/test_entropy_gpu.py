@@ -203,6 +203,20 @@ def test_fallback_shapes(h, w):
     assert torch.equal(_bits(dpa.spectral_entropy_nc(xd, c_begin=1, c_count=2)), _bits(got[:, 1:3]))
 
 
+@pytest.mark.parametrize("h,w", eo.DIRECT_SHAPES, ids=["%dx%d" % s for s in eo.DIRECT_SHAPES])
+def test_fallback_on_the_cosine_matrix_kernels_own_shapes(h, w):
+    """A non-square map with an edge beyond 64 (one of them beyond 256): every coefficient the reduction reads is a dot
+    product of the cosine-matrix kernel. Channels 1 ... 3 of 5 in two samples: the slice is not contiguous."""
+    x = eo.direct_case(h, w)
+    xd = x.to(DEV)
+    got = dpa.spectral_entropy_nc(xd, c_begin=1, c_count=3)
+    _check(got, x, c_begin=1, c_count=3, what="direct %dx%d, channels 1..3 of 5" % (h, w))
+    full = dpa.spectral_entropy_nc(xd)
+    _check(full, x, what="direct %dx%d" % (h, w))
+    assert torch.equal(_bits(got), _bits(full[:, 1:4]))
+    assert torch.equal(_bits(full), _bits(dpa.spectral_entropy_nc(xd, algo=dpa.ALGO_DIRECT)))
+
+
 def test_fallback_pitched_rows_and_direct_against_codelet():
     view = eo.pitch_case(DEV)
     assert view.stride(2) == eo.PITCH and view.stride(3) == 1

@@ -635,6 +635,22 @@ def test_weighted_calls_of_several_shapes_share_one_workspace_safely():
     assert ops._workspace(dev, stream, 1).data_ptr() == base  # one buffer throughout
 
 
+@pytest.mark.parametrize("hw", [(100, 72), (260, 9)])
+def test_weighted_on_the_cosine_matrix_kernels_own_shapes(hw):
+    """A non-square map with an edge beyond 64 (one of them beyond 256): every coefficient that is weighted is a dot product
+    of the cosine-matrix kernel. Channels 1 ... 3 of 5 in two samples (the slice is not contiguous) against float64."""
+    h, w = hw
+    x = synth(2, 5, h, w, 31 * h + w, dead=False)
+    wt = torch.rand(h, w, generator=torch.Generator().manual_seed(h + w))
+    got = dpa.weighted_energy_nc(x.cuda(), wt.cuda(), c_begin=1, c_count=3)
+    ref = torch.from_numpy(orc.weighted_energy_nc_f64(x, wt.numpy(), c_begin=1, c_count=3))
+    err = rel_err(got.cpu(), ref)
+    print("WEIGHTED %dx%d channels 1..3 of 5 worst relative error %.3g" % (h, w, err))
+    assert err <= 2e-5, (hw, err)
+    full = dpa.weighted_energy_nc(x.cuda(), wt.cuda())
+    assert torch.equal(got.view(torch.int32), full[:, 1:4].contiguous().view(torch.int32))
+
+
 @pytest.mark.parametrize("n", [13, 72])
 def test_weighted_chunked_by_a_small_workspace_gives_the_same_bits(n):
     """dcts_weighted_energy_f32 walks every sample in runs of as many channels as its workspace holds coefficient tiles

@@ -23,6 +23,8 @@ CODELET_EDGES = lo.CODELET_EDGES  # every instantiation of k_lowpass_codelet: G 
 FALLBACK = {  # name: (shape of the tensor the view is cut from, K)
     "13x17": ((2, 5, 13, 17), 8), "5x40": ((2, 5, 5, 40), 8), "33x33": ((1, 6, 33, 33), 8), "72x72": ((1, 5, 72, 72), 8),
     "pitched16": ((2, 5, 16, 20), 5),
+    # non-square with an edge beyond 64, one of them beyond 256: the coefficients of the cosine-matrix kernel alone
+    "100x72": ((2, 5, 100, 72), 8), "260x9": ((2, 5, 260, 9), 8),
 }
 
 
