@@ -270,7 +270,7 @@ class _Inception(nn.Module):
 
 class GoogLeNet(nn.Module):
     FILTERS = tuple(_tp.GOOGLENET_FILTERS)
-    REDUCE = ([96, 16], [128, 32], [96, 16], [112, 24], [128, 24], [144, 32], [160, 32], [160, 32], [192, 48])
+    REDUCE = tuple(_tp.GOOGLENET_REDUCE)
     NAMES = ("a3", "b3", "a4", "b4", "c4", "d4", "e4", "a5", "b5")
 
     def __init__(self, num_classes=10, compress_rate=None):

@@ -9,6 +9,11 @@ loader (transplant.py) on the slim net's own state dict and loads the result bac
 the pruning saved. What comes out is what the reference's prune_*.py hold right after load_model (utils/load_models.py
 :775-830) and before their first fine-tuning epoch: fine-tuning, datasets and evaluation stay with the user.
 
+--carry (prune_network(..., carry=True)) is the second mode, for a net that runs before any fine-tuning, for all seven
+architectures: the same rows by the same score files, columns by the data flow of the forward pass
+(transplant.dataflow), conv biases and batch-norm tensors with their channels, everything else brought over; the tool then
+prints output_gap(full, pruned, x) on one synthetic batch as a third line. The default mode is untouched by it.
+
 The tool needs no GPU: the transplant is index_select on whatever device the tensors live on.
 """
 import argparse
@@ -33,7 +38,7 @@ LOADERS = {
 }
 
 
-def prune_network(name, full, imp_score, compress_rate, exact=False):
+def prune_network(name, full, imp_score, compress_rate, exact=False, carry=False):
     """The pruned `name` (an nn.Module in training mode, as constructed) with the kept filters of `full`.
 
     full: the full-width module or its state dict; imp_score: a score directory or a {file stem: scores} dict, as the
@@ -57,16 +62,35 @@ def prune_network(name, full, imp_score, compress_rate, exact=False):
     the block's input; prune_network selects them by the kept filters of what feeds the block
     (transplant_resnet_50(..., downsample_input="block")). With dead filters pruned from the mid channels the result then
     computes what the full net computes; with the reference's choice it differs by 58 % of the largest output
-    (tests/test_pruned_nets_cpu.py). exact=True gives the reference's state dict bit for bit, for resnet_50 too."""
+    (tests/test_pruned_nets_cpu.py). exact=True gives the reference's state dict bit for bit, for resnet_50 too.
+
+    carry=True is the second mode (transplant.transplant_carry), for a net that runs before any
+    fine-tuning, for all seven: rows as above, by the same score files and so with the same masks; a module's input
+    channels by the kept filters of whatever feeds it in the forward pass (transplant.dataflow(name): concatenations in
+    torch.cat order at the original offsets, GoogLeNet's included; after a residual sum the kept list of the block's last
+    conv; the block input for ResNet-50's downsample convs); conv biases and batch-norm tensors with their channels;
+    stems, pre_layers, classifiers, side convs and outconv brought over, a Linear behind pruned features with their
+    kept list as its columns. No tensor keeps its initialisation, so the result does not depend on torch's seed; a conv
+    that kept its width reads no score file, and nothing raises because the reference's control flow would have.
+    With only dead filters removed the result computes what the full net computes wherever the architecture allows it:
+    every rate of vgg_16_bn, googlenet and densenet_40, the mid-channel rates of the three ResNets, the 34 inner rates
+    of u2netp. It cannot for a width that ends in a residual sum - the ResNets' stage outputs, the CIFAR stems with their
+    positional pad-or-crop shortcut, u2netp's five outer widths (d + xin): there each writer of the stream has a kept
+    list of its own, from a score file of its own, and the columns follow the last main-path writer. carry=True with
+    exact=True raises ValueError."""
     if name not in LOADERS:
         raise ValueError("the network name you have entered is not supported yet: %r" % (name,))
+    if carry and exact:
+        raise ValueError("prune_network: carry=True and exact=True exclude each other (exact is the reference's state dict)")
     ori = full.state_dict() if isinstance(full, nn.Module) else full
     like = next((t for t in ori.values() if t.is_floating_point()), None)
     if like is None:
         raise ValueError("prune_network: `full` holds no floating-point tensor")
     net = nets.get_network(name, compress_rate).to(device=like.device, dtype=like.dtype)
     with torch.no_grad():
-        if name == "resnet_50" and not exact:
+        if carry:
+            sd = _tp.transplant_carry(name, net.state_dict(), ori, imp_score)
+        elif name == "resnet_50" and not exact:
             sd = _tp.transplant_resnet_50(net.state_dict(), ori, imp_score, downsample_input="block")
         else:
             sd = LOADERS[name](net.state_dict(), ori, imp_score)
@@ -104,6 +128,24 @@ def cost(net, input_shape):
     return {"params": sum(p.numel() for p in net.parameters()), "macs": macs[0]}
 
 
+def output_gap(full, pruned, x):
+    """max|pruned(x) - full(x)| / max|full(x)| over all outputs (a float): both nets in eval mode and under no_grad, their
+    training flags put back. 0 where the pruning changed nothing the input can show."""
+    flags = full.training, pruned.training
+    full.eval()
+    pruned.eval()
+    try:
+        with torch.no_grad():
+            want, got = full(x), pruned(x)
+    finally:
+        full.train(flags[0])
+        pruned.train(flags[1])
+    want = list(want) if isinstance(want, (tuple, list)) else [want]
+    got = list(got) if isinstance(got, (tuple, list)) else [got]
+    num = max(float((g - w).abs().max()) for g, w in zip(got, want))
+    return num / max(float(w.abs().max()) for w in want)
+
+
 def _report(tag, name, c, base=None):
     line = "%s %s: params %d, MACs %d" % (tag, name, c["params"], c["macs"])
     if base is not None:
@@ -124,15 +166,21 @@ def main(argv=None):
     ap.add_argument("--exact", action="store_true",
                     help="resnet_50: select the downsample convs' input channels as the reference's loader does (by conv2's kept "
                          "filters) instead of by the block input's")
-    ap.add_argument("--out", required=True, help="torch.save target: {'net', 'compress_rate', 'state_dict'}")
+    ap.add_argument("--carry", action="store_true",
+                    help="columns by data flow, biases and batch-norms with their channels, everything else brought over: a net "
+                         "that runs before fine-tuning (all seven nets); prints max|pruned - full| / max|full| on one "
+                         "synthetic batch seeded by --seed as a third line")
+    ap.add_argument("--out", required=True, help="torch.save target: {'net', 'compress_rate', 'carry', 'state_dict'}")
     args = ap.parse_args(argv)
+    if args.carry and args.exact:
+        ap.error("--carry and --exact exclude each other")
     torch.manual_seed(args.seed)
     try:
         rates = parse_compress_rate(args.compress_rate)
         full = nets.get_network(args.net)
         if args.pretrain_dir:
             nets.load_checkpoint(full, types.SimpleNamespace(net=args.net, pretrain_dir=args.pretrain_dir))
-        pruned = prune_network(args.net, full, args.imp_score, rates, exact=args.exact)
+        pruned = prune_network(args.net, full, args.imp_score, rates, exact=args.exact, carry=args.carry)
     except (ValueError, OSError) as exc:  # short rate list, wrong-length or missing score file, unreadable checkpoint
         ap.error(str(exc))
     shape = list(INPUT_SHAPES[NET_DATASET[args.net]])
@@ -141,7 +189,11 @@ def main(argv=None):
     base = cost(full, shape)
     print(_report("full  ", args.net, base))
     print(_report("pruned", args.net, cost(pruned, shape), base))
-    torch.save({"net": args.net, "compress_rate": rates,
+    if args.carry:
+        from .data import SyntheticLoader
+        x = next(iter(SyntheticLoader(shape, 2, 1, seed=args.seed)))[0]
+        print("gap    %s: max|pruned - full| / max|full| %.3g on one synthetic batch" % (args.net, output_gap(full, pruned, x)))
+    torch.save({"net": args.net, "compress_rate": rates, "carry": bool(args.carry),
                 "state_dict": {k: v.detach().cpu() for k, v in pruned.state_dict().items()}}, args.out)
     return 0
 

@@ -41,12 +41,21 @@ Quirks kept because the result must equal the reference's state dict:
     copied either, the other batch-norms (four tensors, not num_batches_tracked) and the linear layer
     come over whole (:361-380).
 
+  * U^2-Net-p: only conv weights are written, and the control flow raises for ordinary rate lists: with every rate 0 a
+    stage starts with no live index and list(None) is evaluated (:617 / :621); with inner widths pruned only, the first
+    decoder stage's un-pruned rebnconvin behind a pruned unit evaluates int('i') (:658).
+
+Beside these loaders stands the carry mode (dataflow, transplant_carry, at the end of this file): the same rows
+by the same score files, but input channels by the data flow of nets.py's forward passes, per-channel tensors with their
+channels and every other tensor brought over - one table per net and one copy routine, none of the quirks above.
+
 Widths of the pruned networks (what `currentfilter_num` is) follow the model constructors:
 models/cifar10/vgg.py:37, models/cifar10/resnet.py:5-30 and models/imagenet/resnet.py:8-27 (adapt_channel),
 models/cifar10/densenet.py:71-75, :91-104, models/cifar10/googlenet.py:28-66, :147-149.
 """
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -597,3 +606,235 @@ def transplant_u2netp(state_dict, oristate_dict, imp_score, conv_names=None):
                 state_dict[key] = ori
             last = saved_side[5 - cnt]                                                   # :767
     return state_dict
+
+
+# ---------------------------------------------------------------------------------------------
+# The carry mode: rows by the score files, columns by data flow, per-channel tensors with their channels
+# ---------------------------------------------------------------------------------------------
+GOOGLENET_REDUCE = [[96, 16], [128, 32], [96, 16], [112, 24], [128, 24], [144, 32], [160, 32], [160, 32], [192, 48]]  # models/cifar10/googlenet.py:171-184
+
+Flow = namedtuple("Flow", "module kind stem width sources")
+Flow.__doc__ = """One parameterised module of a net's data flow (DESIGN.md §7m).
+
+module   the module's name below the net: its tensors are module + ".weight" and so on
+kind     "conv" (Conv2d), "bn" (BatchNorm1d / 2d) or "linear" (Linear)
+stem     conv: the score file that selects its ROWS once its width shrank (the file the reference's loader reads for
+         that conv); None for a conv no constructor shrinks, for batch-norms and for linear layers
+width    output channels of the module in the full-width net (bn: its channels)
+sources  whose kept filters make up the module's INPUT channels (bn: its channels), as ((producer conv, offset), ...)
+         in channel order: the producer's kept list shifted by its offset in the ORIGINAL tensor. () is an input that
+         never shrinks and comes whole: the net's own, or VGG's classifier behind its first Linear. A linear layer's columns are its sources' channels (every net pools to 1 x 1 first)."""
+
+
+def _conv_bn(out, conv, bn, stem, width, sources):
+    out.append(Flow(conv, "conv", stem, width, tuple(sources)))
+    out.append(Flow(bn, "bn", None, width, ((conv, 0),)))
+
+
+def _flow_vgg_16_bn():
+    out, prev = [], ()
+    idx = [i for i, x in enumerate(VGG_CFG) if x != "M"]
+    for k, i in enumerate(idx):
+        # the 13th conv has no rate of its own (vgg_16_bn_widths): no file
+        _conv_bn(out, "features.conv%d" % i, "features.norm%d" % i, "imp_conv%d" % (k + 1) if k < len(idx) - 1 else None,
+                 VGG_CFG[i], prev)
+        prev = (("features.conv%d" % i, 0),)
+    out.append(Flow("classifier.linear1", "linear", None, 512, prev))
+    out.append(Flow("classifier.norm1", "bn", None, 512, ()))
+    out.append(Flow("classifier.linear2", "linear", None, 10, ()))
+    return out
+
+
+def _flow_resnet_cifar(num_layers):
+    stage_out = _resnet_cifar_stage_out(num_layers)
+    out = []
+    _conv_bn(out, "conv1", "bn1", "imp_conv1", stage_out[0], ())
+    stream = (("conv1", 0),)  # the residual stream: written last by the stem, then by each block's conv2
+    for conv, stem, blk, kind in resnet_cifar_convs(num_layers):
+        _conv_bn(out, conv, conv.replace(".conv", ".bn"), stem, stage_out[blk + 1], stream)
+        stream = ((conv, 0),)  # conv2 reads conv1; the next block reads this block's conv2
+    out.append(Flow("fc" if num_layers == 56 else "linear", "linear", None, 10, stream))
+    return out
+
+
+def _flow_resnet_50():
+    out, stream, block_in, held = [], (), (), []
+    for k, (conv, bn, _, blk, kind) in enumerate(resnet_50_convs()):
+        width = RESNET50_STAGE_OUT[0] if kind == "stem" else RESNET50_STAGE_OUT[blk + 1] // (4 if kind == "mid" else 1)
+        if conv.endswith(".0.conv1"):
+            block_in = stream  # what a stage's first block is entered with: its conv1 and its downsample conv read it
+        if kind == "downsample":  # the loader's file order has it before conv3, the module order behind it
+            _conv_bn(held, conv, bn, "imp_conv%d" % (k + 1), width, block_in)
+            continue
+        _conv_bn(out, conv, bn, "imp_conv%d" % (k + 1), width, stream)
+        stream = ((conv, 0),)
+        out += held
+        del held[:]
+    out.append(Flow("fc", "linear", None, 1000, stream))
+    return out
+
+
+def _flow_densenet_40():
+    names = densenet_40_conv_names()
+    widths = densenet_40_widths([0.0] * 39)
+    out = [Flow("conv1", "conv", "imp_conv1", widths[0], ())]
+    cat, off = [("conv1", 0)], widths[0]  # the growing concatenation, restarted at conv1 and after each transition
+    for cov_id, (name, w) in enumerate(zip(names[1:], widths[1:]), start=2):
+        base = name[:-len("conv1")]
+        out.append(Flow(base + "bn1", "bn", None, off, tuple(cat)))
+        out.append(Flow(name, "conv", "imp_conv%d" % cov_id, w, tuple(cat)))
+        if name.startswith("trans"):
+            cat, off = [(name, 0)], w
+        else:
+            cat.append((name, off))
+            off += w
+    out.append(Flow("bn", "bn", None, off, tuple(cat)))
+    out.append(Flow("fc", "linear", None, 10, tuple(cat)))
+    return out
+
+
+def _flow_googlenet():
+    out = []
+    _conv_bn(out, "pre_layers.0", "pre_layers.1", None, 192, ())
+    prev = (("pre_layers.0", 0),)
+    for b, (name, f, r) in enumerate(zip(GOOGLENET_BLOCKS, GOOGLENET_FILTERS, GOOGLENET_REDUCE)):
+        n3, n5 = "imp_conv%d_n3x3" % (b + 2), "imp_conv%d_n5x5" % (b + 2)
+        p = name + "."
+        _conv_bn(out, p + "branch1x1.0", p + "branch1x1.1", None, f[0], prev)
+        _conv_bn(out, p + "branch3x3.0", p + "branch3x3.1", None, r[0], prev)
+        _conv_bn(out, p + "branch3x3.3", p + "branch3x3.4", n3, f[1], ((p + "branch3x3.0", 0),))
+        _conv_bn(out, p + "branch5x5.0", p + "branch5x5.1", None, r[1], prev)
+        _conv_bn(out, p + "branch5x5.3", p + "branch5x5.4", n5, f[2], ((p + "branch5x5.0", 0),))
+        _conv_bn(out, p + "branch5x5.6", p + "branch5x5.7", n5, f[2], ((p + "branch5x5.3", 0),))  # one file, both convs
+        _conv_bn(out, p + "branch_pool.1", p + "branch_pool.2", None, f[3], prev)
+        # torch.cat order: 1x1, 3x3, 5x5, pool
+        prev = ((p + "branch1x1.0", 0), (p + "branch3x3.3", f[0]), (p + "branch5x5.6", f[0] + f[1]),
+                (p + "branch_pool.1", f[0] + f[1] + f[2]))
+    out.append(Flow("linear", "linear", None, 10, prev))
+    return out
+
+
+def _flow_u2netp():
+    width = {n: o for n, o, _ in u2netp_conv_shapes([0.0] * 39)}
+    out = []
+
+    def unit(prefix, name, sources):
+        conv = "%s.%s.conv_s1" % (prefix, name)
+        _conv_bn(out, conv, "%s.%s.bn_s1" % (prefix, name), "net.%s.%s.relu_s1" % (prefix, name), width[conv], sources)
+        return conv
+
+    def rsu(prefix, depth, sources):
+        """The units in module order; returns the conv that writes the stage's output last (d + xin: rebnconv1d)."""
+        enc = [unit(prefix, "rebnconvin", sources)]
+        for k in range(1, depth + 1):
+            enc.append(unit(prefix, "rebnconv%d" % k, ((enc[-1], 0),)))
+        d = enc[-1]
+        for k in range(depth - 1, 0, -1):
+            d = unit(prefix, "rebnconv%dd" % k, ((d, 0), (enc[k], width[d])))  # torch.cat((d, enc[k - 1])), enc[0] is xin here
+        return d
+
+    h, prev = {}, ()
+    for s in range(1, 7):
+        h[s] = rsu("stage%d" % s, U2NETP_DEPTH[s], prev)
+        prev = ((h[s], 0),)
+    d, deeper = {}, h[6]
+    for s in range(5, 0, -1):
+        d[s] = rsu("stage%dd" % s, U2NETP_DEPTH[s], ((deeper, 0), (h[s], width[deeper])))  # torch.cat((up(deeper), h_s))
+        deeper = d[s]
+    for k, src in zip(range(1, 7), (d[1], d[2], d[3], d[4], d[5], h[6])):
+        out.append(Flow("side%d" % k, "conv", None, 1, ((src, 0),)))
+    out.append(Flow("outconv", "conv", None, 1, tuple(("side%d" % k, k - 1) for k in range(1, 7))))
+    return out
+
+
+_DATAFLOW = {"vgg_16_bn": _flow_vgg_16_bn, "resnet_56": lambda: _flow_resnet_cifar(56), "resnet_110": lambda: _flow_resnet_cifar(110),
+             "densenet_40": _flow_densenet_40, "googlenet": _flow_googlenet, "resnet_50": _flow_resnet_50, "u2netp": _flow_u2netp}
+
+
+def dataflow(name):
+    """[Flow] for every parameterised module of `name`, in state-dict order: which score file selects a conv's rows,
+    and from which producers, at which offsets of the original tensor, a module's input channels come. The table does
+    not depend on the rates: it is derived from the constants the width functions use (VGG_CFG, RESNET_CIFAR_REPEAT,
+    RESNET50_STAGE_OUT, DENSENET40_GROWTH, GOOGLENET_FILTERS, U2NETP_DEPTH) and from the forward passes of nets.py.
+
+    Pooling, up-sampling and activations are transparent; a concatenation lists its parts in torch.cat order; after a
+    residual sum the stream carries the kept list of the main-path conv that wrote it last (the block's last conv, an
+    RSU's rebnconv1d), the stem's for the first block; ResNet-50's downsample convs read the block's input."""
+    if name not in _DATAFLOW:
+        raise ValueError("the network name you have entered is not supported yet: %r" % (name,))
+    return _DATAFLOW[name]()
+
+
+def _channels(sources, kept):
+    """The original channel indices a module with these sources still reads (None: the net's input, whole)."""
+    if not sources:
+        return None
+    return np.concatenate([np.asarray(kept[p], dtype=np.int64) + off for p, off in sources])
+
+
+def transplant_carry(name, state_dict, oristate_dict, imp_score):
+    """The carry mode: a new state dict with the keys, order and shapes of `state_dict` (the slim
+    net's, read for its shapes only: none of its values survives) and the values of `oristate_dict`, copied by
+    dataflow(name):
+
+      1. a conv whose width shrank keeps select_index(scores of its file, original width, slim width) rows, a conv
+         that kept its width keeps every row and its file is not read;
+      2. input channels are the kept filters of the module's sources, each shifted by its offset in the original tensor;
+      3. conv biases and the batch-norm tensors behind a conv take the conv's rows, a batch-norm in front of a conv
+         the kept channels of its input; every num_batches_tracked is copied;
+      4. everything else - stems, classifiers, side convs - comes over, a Linear behind pruned features with their
+         kept list as its columns.
+
+    Where a width ends in a residual sum (the CIFAR stems and stage outputs, ResNet-50's stage outputs, U2-Net-p's
+    five outer widths) every writer of the stream has a kept list from a score file of its own and rule 2 follows the
+    last main-path writer: there the pruned net is not the full net with dead filters removed, whatever the scores.
+    A shape that the table cannot produce (a conv without a score file that lost filters, a Linear whose columns
+    are not one per channel) raises ValueError."""
+    table = dataflow(name)
+    kept = {}
+    for f in table:
+        if f.kind != "conv":
+            continue
+        ori, cur = oristate_dict[f.module + ".weight"], state_dict[f.module + ".weight"]
+        o, c = ori.size(0), cur.size(0)
+        if o != f.width:
+            raise ValueError("%s has %d filters in the full net, the %s table says %d" % (f.module, o, name, f.width))
+        if c == o:
+            kept[f.module] = np.arange(o)
+        elif f.stem is None:
+            raise ValueError("%s lost filters (%d of %d left) and has no score file" % (f.module, c, o))
+        else:
+            kept[f.module] = _kept_rows(imp_score, f.stem, o, c)
+    out = {}
+
+    def take(key, rows, cols=None):
+        t = oristate_dict[key]
+        if rows is not None and len(rows) == t.size(0):
+            rows = None  # nothing removed on this axis: the tensor itself
+        if cols is not None and len(cols) == t.size(1):
+            cols = None
+        out[key] = _rows_cols(t, rows, cols).clone() if (rows is not None or cols is not None) else t.clone()
+
+    for f in table:
+        chan = _channels(f.sources, kept)
+        if f.kind == "conv":
+            take(f.module + ".weight", kept[f.module], chan)
+            if f.module + ".bias" in oristate_dict:
+                take(f.module + ".bias", kept[f.module])
+        elif f.kind == "bn":
+            for part in _BN_PARTS:
+                take(f.module + part, chan)
+            out[f.module + ".num_batches_tracked"] = oristate_dict[f.module + ".num_batches_tracked"].clone()
+        else:
+            w = oristate_dict[f.module + ".weight"]
+            if chan is not None and w.size(1) != sum(next(g.width for g in table if g.module == p) for p, _ in f.sources):
+                raise ValueError("%s reads %d columns, not one per channel of its input" % (f.module, w.size(1)))
+            take(f.module + ".weight", None, chan)
+            take(f.module + ".bias", None)
+    missing = [k for k in state_dict if k not in out]
+    if missing:
+        raise ValueError("the %s table does not cover %s" % (name, ", ".join(missing[:4])))
+    for k, t in state_dict.items():
+        if out[k].shape != t.shape:
+            raise ValueError("%s: the table gives %s, the pruned net holds %s" % (k, list(out[k].shape), list(t.shape)))
+    return type(state_dict)((k, out[k]) for k in state_dict)
