@@ -14,6 +14,13 @@ architectures: the same rows by the same score files, columns b
 (transplant.dataflow), conv biases and batch-norm tensors with their channels, everything else brought over; the tool then
 prints output_gap(full, pruned, x) on one synthetic batch as a third line. The default mode is untouched by it.
 
+--carry --compensate (prune_network(..., carry=True, moments=...)) goes one step further (compensate.py): carry
+drops what a removed filter fed into the next layer, which is exact for dead filters only. The tool sweeps --calib_batches
+batches of --batch_size samples through the full net once (compensate.collect_moments: the second moments of every consumer's
+input), fits each removed input channel as a linear combination of the kept ones and folds the fit into the consumer's
+weights; no bias or batch-norm tensor changes. A fourth line reports the gap after the merge, on the third line's batch,
+and the largest residual of the fits.
+
 The tool needs no GPU: the transplant is index_select on whatever device the tensors live on.
 """
 import argparse
@@ -38,7 +45,7 @@ LOADERS = {
 }
 
 
-def prune_network(name, full, imp_score, compress_rate, exact=False, carry=False):
+def prune_network(name, full, imp_score, compress_rate, exact=False, carry=False, moments=None, rtol=1e-10):
     """The pruned `name` (an nn.Module in training mode, as constructed) with the kept filters of `full`.
 
     full: the full-width module or its state dict; imp_score: a score directory or a {file stem: scores} dict, as the
@@ -77,11 +84,19 @@ def prune_network(name, full, imp_score, compress_rate, exact=False, carry=False
     of u2netp. It cannot for a width that ends in a residual sum - the ResNets' stage outputs, the CIFAR stems with their
     positional pad-or-crop shortcut, u2netp's five outer widths (d + xin): there each writer of the stream has a kept
     list of its own, from a score file of its own, and the columns follow the last main-path writer. carry=True with
-    exact=True raises ValueError."""
+    exact=True raises ValueError.
+
+    moments (with carry=True; ValueError without) compensates the prune: compensate.collect_moments(name,
+    full, batches, compress_rate) gives the second moments of every consumer's input over a few calibration batches, and
+    compensate.compensate then adds to each consumer's kept columns the least-squares image of the removed ones,
+    W_S + W_D M_DS pinv(M_SS, rtol). A removed filter whose map is a linear combination of kept maps then goes without a
+    trace too, not only a dead one; consumer weights change, nothing else. With moments=None the result is carry's."""
     if name not in LOADERS:
         raise ValueError("the network name you have entered is not supported yet: %r" % (name,))
     if carry and exact:
         raise ValueError("prune_network: carry=True and exact=True exclude each other (exact is the reference's state dict)")
+    if moments is not None and not carry:
+        raise ValueError("prune_network: moments compensate the carry mode, pass carry=True with them")
     ori = full.state_dict() if isinstance(full, nn.Module) else full
     like = next((t for t in ori.values() if t.is_floating_point()), None)
     if like is None:
@@ -95,6 +110,9 @@ def prune_network(name, full, imp_score, compress_rate, exact=False, carry=False
         else:
             sd = LOADERS[name](net.state_dict(), ori, imp_score)
         net.load_state_dict(sd, strict=True)
+    if moments is not None:
+        from .compensate import compensate
+        compensate(name, net, ori, imp_score, moments, rtol=rtol)
     return net
 
 
@@ -170,10 +188,25 @@ def main(argv=None):
                     help="columns by data flow, biases and batch-norms with their channels, everything else brought over: a net "
                          "that runs before fine-tuning (all seven nets); prints max|pruned - full| / max|full| on one "
                          "synthetic batch seeded by --seed as a third line")
-    ap.add_argument("--out", required=True, help="torch.save target: {'net', 'compress_rate', 'carry', 'state_dict'}")
+    ap.add_argument("--compensate", action="store_true",
+                    help="with --carry: fit every removed input channel as a linear combination of the kept ones on calibration "
+                         "batches and fold the fit into the consumer's weights; prints the gap after it and the largest "
+                         "residual as a fourth line")
+    ap.add_argument("--calib_batches", type=int, default=4, help="--compensate: number of calibration batches")
+    ap.add_argument("--batch_size", type=int, default=64, help="--compensate: samples per calibration batch")
+    ap.add_argument("--synthetic", action="store_true", help="--compensate: synthetic batches of the dataset's shape, seeded by --seed + 1 (not the gap's batch)")
+    ap.add_argument("--dataset", default=None, choices=("cifar10", "imagenet", "DUTS", "synthetic"),
+                    help="--compensate: where the calibration batches come from (default: the net's dataset)")
+    ap.add_argument("--data_dir", default="./data", help="--compensate: path to the dataset")
+    ap.add_argument("--out", required=True,
+                    help="torch.save target: {'net', 'compress_rate', 'carry', 'compensate', 'state_dict'}")
     args = ap.parse_args(argv)
     if args.carry and args.exact:
         ap.error("--carry and --exact exclude each other")
+    if args.compensate and not args.carry:
+        ap.error("--compensate needs --carry")
+    if args.compensate and args.calib_batches < 1:
+        ap.error("--calib_batches is at least 1")
     torch.manual_seed(args.seed)
     try:
         rates = parse_compress_rate(args.compress_rate)
@@ -193,7 +226,21 @@ def main(argv=None):
         from .data import SyntheticLoader
         x = next(iter(SyntheticLoader(shape, 2, 1, seed=args.seed)))[0]
         print("gap    %s: max|pruned - full| / max|full| %.3g on one synthetic batch" % (args.net, output_gap(full, pruned, x)))
-    torch.save({"net": args.net, "compress_rate": rates, "carry": bool(args.carry),
+    if args.compensate:
+        import itertools
+        from . import compensate as _cp
+        from .data import load_data
+        try:  # synthetic batches by --seed + 1: the batch the gaps are taken on is not among them
+            loader, _ = load_data(types.SimpleNamespace(
+                net=args.net, dataset=args.dataset or NET_DATASET[args.net], synthetic=args.synthetic, data_dir=args.data_dir,
+                batch_size=args.batch_size, limit=args.calib_batches, input_size=args.input_size, seed=args.seed + 1))
+        except RuntimeError as exc:  # a real dataset without torchvision
+            ap.error(str(exc))
+        moments = _cp.collect_moments(args.net, full, itertools.islice(loader, args.calib_batches), rates)
+        merged = _cp.compensate(args.net, pruned, full, args.imp_score, moments)
+        print("merged %s: max|pruned - full| / max|full| %.3g on the same batch, largest residual %.3g over %d modules"
+              % (args.net, output_gap(full, pruned, x), max([m.residual for m in merged] + [0.0]), len(merged)))
+    torch.save({"net": args.net, "compress_rate": rates, "carry": bool(args.carry), "compensate": bool(args.compensate),
                 "state_dict": {k: v.detach().cpu() for k, v in pruned.state_dict().items()}}, args.out)
     return 0
 

@@ -772,6 +772,27 @@ def _channels(sources, kept):
     return np.concatenate([np.asarray(kept[p], dtype=np.int64) + off for p, off in sources])
 
 
+def kept_filters(name, state_dict, oristate_dict, imp_score):
+    """{conv module: the rows of the full conv that the slim one keeps (ascending int64 indices)} for every conv of
+    dataflow(name): rule 1 of transplant_carry, which compensate.compensate reads too. `state_dict` is read for its
+    shapes only."""
+    kept = {}
+    for f in dataflow(name):
+        if f.kind != "conv":
+            continue
+        ori, cur = oristate_dict[f.module + ".weight"], state_dict[f.module + ".weight"]
+        o, c = ori.size(0), cur.size(0)
+        if o != f.width:
+            raise ValueError("%s has %d filters in the full net, the %s table says %d" % (f.module, o, name, f.width))
+        if c == o:
+            kept[f.module] = np.arange(o)
+        elif f.stem is None:
+            raise ValueError("%s lost filters (%d of %d left) and has no score file" % (f.module, c, o))
+        else:
+            kept[f.module] = _kept_rows(imp_score, f.stem, o, c)
+    return kept
+
+
 def transplant_carry(name, state_dict, oristate_dict, imp_score):
     """The carry mode: a new state dict with the keys, order and shapes of `state_dict` (the slim
     net's, read for its shapes only: none of its values survives) and the values of `oristate_dict`, copied by
@@ -791,20 +812,7 @@ def transplant_carry(name, state_dict, oristate_dict, imp_score):
     A shape that the table cannot produce (a conv without a score file that lost filters, a Linear whose columns
     are not one per channel) raises ValueError."""
     table = dataflow(name)
-    kept = {}
-    for f in table:
-        if f.kind != "conv":
-            continue
-        ori, cur = oristate_dict[f.module + ".weight"], state_dict[f.module + ".weight"]
-        o, c = ori.size(0), cur.size(0)
-        if o != f.width:
-            raise ValueError("%s has %d filters in the full net, the %s table says %d" % (f.module, o, name, f.width))
-        if c == o:
-            kept[f.module] = np.arange(o)
-        elif f.stem is None:
-            raise ValueError("%s lost filters (%d of %d left) and has no score file" % (f.module, c, o))
-        else:
-            kept[f.module] = _kept_rows(imp_score, f.stem, o, c)
+    kept = kept_filters(name, state_dict, oristate_dict, imp_score)
     out = {}
 
     def take(key, rows, cols=None):
