@@ -53,6 +53,7 @@ Widths of the pruned networks (what `currentfilter_num` is) follow the model con
 models/cifar10/vgg.py:37, models/cifar10/resnet.py:5-30 and models/imagenet/resnet.py:8-27 (adapt_channel),
 models/cifar10/densenet.py:71-75, :91-104, models/cifar10/googlenet.py:28-66, :147-149.
 """
+import functools
 import math
 import os
 from collections import namedtuple
@@ -103,6 +104,7 @@ def resnet_50_widths(compress_rate):
     return overall, mid
 
 
+@functools.lru_cache(None)  # the rate solver (rates.py) asks thousands of times: callers read the list, none writes it
 def resnet_50_convs():
     """The convolutions in the order load_resnet_imagenet_model visits them (utils/load_models.py:457-512):
     (conv name, bn name, record_last, block index or None, kind) with kind in
@@ -164,6 +166,7 @@ def resnet_cifar_widths(compress_rate, num_layers):
     return overall, mid
 
 
+@functools.lru_cache(None)
 def resnet_cifar_convs(num_layers):
     """[(conv name, score file stem, block index, 'mid' | 'out')] in the order load_resnet_model visits
     them (utils/load_models.py:83-94): score file cnt with cnt = 2, 3, ... (imp_conv1 is the stem's)."""
